@@ -14,8 +14,23 @@ consistency and selection-weight bookkeeping) + one RCCL all-gather of the
 winning trajectories when N_gpus > 1 (scenes are sharded, weak scaling).
 Scene data is uploaded once before the timed region (inputs resident in HBM).
 
-    python bench.py [--gpus N --steps K --warmup W] [--config C2|C3|C4|C5]
+    python bench.py [--gpus N --steps K --warmup W] [--config C2|C3|C4|C5] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
+
+A plain run does what the headline figure needs and no more: it builds the seeded batch, runs the
+W warm-up steps and the K timed steps, writes the last step's outputs if `--dump-outputs DIR` is
+given, and prints the line (`value`, `ms_per_step`, and the figures that come out of the timed
+steps themselves: `phases_ms` and `roofline` from the steps' own HIP events, `solver_stats` from
+the last step's outputs).  `--full` adds the legs that take runs of their own: the other QP
+profile on the same batch (`qp_profile_alt`, `--alt-steps`), the CPU baseline and the oracle
+parity check (`cpu_baseline`, `vs_cpu_baseline`, `parity`; `--no-cpu` skips them), and the rare
+interior-point passes in `roofline.flop_per_solve`, which are priced at the oracle sample's rates.
+
+`--dump-outputs DIR` writes what the last timed step handed to its caller, one float64
+`DIR/<name>.npy` each: the batched solve's `xtraj`, `utraj`, `pobj`, `exit` and `info`, the
+per-scene `winners` records (C5: and the pick `best`), at N > 1 rank 0's `gathered` records.  The
+batch is seeded, so the same arguments give the same inputs in every run.  Above 64 MB in all,
+every array keeps the same seeded sample of its rows (dump_outputs).
 
 `--gpus N > 1` without a launcher (no WORLD_SIZE in the environment) starts the N
 rank processes itself: torch.distributed.run as a CHILD process (one rank per GPU,
@@ -28,7 +43,7 @@ iterations each solve executed; the path is fp64-latency bound, DESIGN.md §3);
 `roofline.hbm` prices it against HBM with SURVEY.md §8(d)'s algorithmic bytes
 per solve; `roofline.traffic` comes from the rocprofv3 PMC
 summary under profiles/ only when that summary was taken on the same kernel
-sources (source hash), else it is null.  `cpu_baseline` times the C oracle
+sources (source hash), else it is null.  With `--full`, `cpu_baseline` times the C oracle
 (same algorithm, OpenMP over solves) on a bounded sample of the same batch
 (rank 0, N=1), and `parity` is the oracle check of that sample; at N>1 every
 rank checks a sample of its own shard and the results are reduced over ranks.
@@ -65,6 +80,34 @@ DEFAULT_SCENES = {"C1": 1024, "C2": 1024, "C3": 4096, "C4": 2048, "C5": 2048, "J
 DEFAULT_GUESSES = {"JS": 5, "JD": 5}
 CHECK_CHUNK = 256              # solves per oracle call in the check leg
 RANK_SAMPLE = 256              # solves each rank checks at N > 1
+DUMP_BUDGET = 64 * 10**6       # bytes --dump-outputs may write in all
+DUMP_SEED = 20251212           # of the row sample of a larger output
+
+
+def dump_outputs(path, arrays, budget=DUMP_BUDGET, seed=DUMP_SEED):
+    """--dump-outputs: every array of `arrays` (name -> numpy array, leading axis = solve or scene)
+    as float64 `path/<name>.npy` (the integer outputs exit / info / best are exact in float64).
+    If they hold more than `budget` bytes in all, each array keeps a sample of its rows in the same
+    proportion, drawn without replacement from a generator seeded with `seed` (one draw per row
+    count, in ascending row order), so two runs with the same arguments write the same rows.
+    Returns name -> rows written."""
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    total = sum(a.size * 8 for a in arrays.values())
+    # 128 bytes per file cover the .npy header
+    room = budget - 128 * len(arrays)
+    frac = 1.0 if total <= room else room / total
+    os.makedirs(path, exist_ok=True)
+    picks, rows = {}, {}
+    for name, a in arrays.items():
+        n = a.shape[0]
+        if frac < 1.0:
+            k = max(1, int(n * frac))
+            if n not in picks:
+                picks[n] = np.sort(np.random.default_rng([seed, n]).choice(n, size=k, replace=False))
+            a = a[picks[n]]
+        rows[name] = int(a.shape[0])
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    return rows
 
 
 def algorithmic_bytes_per_solve(lay):
@@ -202,6 +245,16 @@ class Workload:
         from oscar_mpc_planner_mr_modification_amd.distributed import gather_winners
         if self.world > 1:
             gather_winners(winners, self.world, out=self.gathered)
+
+    def outputs(self):
+        """what the last step handed to its caller (device tensors): the batched solve's outputs,
+        the per-scene winner records and, at N > 1, the gathered records of every rank"""
+        o = dict(self.out, winners=self.winners)
+        if getattr(self, "best", None) is not None:
+            o["best"] = self.best
+        if self.gathered is not None:
+            o["gathered"] = self.gathered
+        return o
 
 
 class TmpcWorkload(Workload):
@@ -476,13 +529,20 @@ def main():
     ap.add_argument("--qp-profile", default="hpipm", choices=("hpipm", "robust"),
                     help="the interior point (DESIGN.md §2.2): hpipm = HPIPM's BALANCE mode as acados configures "
                          "it (the reference's configuration, default), robust = round 4's constants")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs that take runs of their own: the other QP profile "
+                         "(--alt-steps), the CPU baseline and the oracle parity check (--no-cpu skips these two)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's outputs as DIR/<name>.npy (float64, at most 64 MB in all)")
     ap.add_argument("--alt-steps", type=int, default=10,
-                    help="N=1: also time this many steps with the other QP profile (0: skip)")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="bound of the CPU-baseline sample")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the oracle (CPU baseline and parity)")
+                    help="--full, N=1: also time this many steps with the other QP profile (0: skip)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: bound of the CPU-baseline sample")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the oracle (CPU baseline and parity)")
     ap.add_argument("--traffic-json", default=None, help="PMC summary (default profiles/traffic_<config>.json)")
     ap.add_argument("--spawn-check", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.guesses is None:
         args.guesses = DEFAULT_GUESSES.get(args.config, 8)
     if args.traffic_json is None:
@@ -560,10 +620,14 @@ def main():
         elapsed = float(te[0])
         phase_ms = {p: float(te[1 + j]) for j, p in enumerate(wl.phases)}
     kern_ms = phase_ms["solve"]
-    # the other QP profile on the same batch (N = 1, after the timed region): the delta between the
-    # reference's interior point and the robust one
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # the last timed step's outputs, before any other leg runs on the same buffers
+        dumped = dump_outputs(args.dump_outputs, {k: v.cpu().numpy() for k, v in wl.outputs().items()})
+    # --full: the other QP profile on the same batch (N = 1, after the timed region): the delta
+    # between the reference's interior point and the robust one
     alt = None
-    if world == 1 and args.alt_steps > 0:
+    if args.full and world == 1 and args.alt_steps > 0:
         other = "robust" if args.qp_profile == "hpipm" else "hpipm"
         pr_main = wl.pr
         wl.pr = native_problem(lay, args, other)
@@ -690,7 +754,10 @@ def main():
         result["rehearsal"] = {"backend": "gloo", "ranks": world, "devices": min(world, n_dev),
                                "rate_is_scaling_figure": False}
 
-    if not args.no_cpu:
+    if dumped is not None:
+        result["dumped_outputs"] = {"dir": args.dump_outputs, "dtype": "float64", "rows": dumped}
+
+    if args.full and not args.no_cpu:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import oracle_py
 

@@ -4,7 +4,7 @@
     python scripts/ab_bench.py --run base,bsel --configs C2,C3,C4 [--reps 2]  # GPU: bench each
 
 Each variant is a full libmpcg.so under build/ab/<name>/ with the given extra flags; the
-GPU side runs bench.py (no CPU leg) once per (rep, variant, config), alternating variants,
+GPU side runs bench.py --full (no CPU leg) once per (rep, variant, config), alternating variants,
 in child processes with MPCG_LIB set, and prints one JSON line each."""
 import argparse
 import json
@@ -44,7 +44,7 @@ def main():
             for name in args.run.split(","):
                 # (an earlier round's library, ABI 8: its mpcg_problem is a prefix of ABI 9's)
                 env = dict(os.environ, MPCG_LIB=lib(name), MPCG_ABI_ACCEPT_OLDER="8")
-                r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", cfg, "--no-cpu",
+                r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", cfg, "--full", "--no-cpu",
                                     "--steps", str(args.steps), "--warmup", "2"], env=env, capture_output=True,
                                    text=True, timeout=600)
                 line = [x for x in r.stdout.splitlines() if x.startswith("{")]

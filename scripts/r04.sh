@@ -4,6 +4,7 @@
 #   bash scripts/r04.sh trace parity sqp tests smoke bench profile
 mkdir -p gpurun_out
 export PYTHONUNBUFFERED=1
+bench_out=${BENCH_OUT:-bench_out}; mkdir -p $bench_out   # where the bench step writes its lines
 tag=${R04_TAG:-r04}
 step() {  # step <name> <seconds> <output file> <command...>
   local name=$1 secs=$2 out=$3; shift 3
@@ -29,7 +30,7 @@ for s in "$@"; do
       step smoke 300 gpurun_out/${tag}_smoke.log python -u -c "import __graft_entry__ as g; g.smoke()" ;;
     bench)
       for c in ${R04_BENCH:-C2}; do
-        step bench_$c 600 gpurun_out/${tag}_bench_$(echo $c | tr A-Z a-z).json python -u bench.py --config $c --steps 20 --warmup 5
+        step bench_$c 600 $bench_out/${tag}_bench_$(echo $c | tr A-Z a-z).json python -u bench.py --config $c --full --steps 20 --warmup 5
       done ;;
     latency)  # one Solver::solve() / one GuidanceConstraints::optimize through the drop-in's context
       step latency_js 300 gpurun_out/${tag}_latency_js.json python -u scripts/latency.py --config JS --guesses 5

@@ -6,6 +6,8 @@ import os
 import subprocess
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -66,6 +68,72 @@ def test_unknown_collective_backend_is_refused():
     r = subprocess.run([sys.executable, "bench.py"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=120)
     assert r.returncode != 0
     assert "MPCG_BENCH_BACKEND=mpi" in r.stderr
+
+
+def test_dump_outputs_writes_float64_and_samples_a_larger_output(tmp_path):
+    """--dump-outputs: one float64 <name>.npy per output, integers exact; above the byte budget
+    every array keeps the same seeded rows (arrays of one row count the same rows), the files
+    stay within the budget, and a second call writes the same bytes"""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(7)
+    arrays = {"xtraj": rng.standard_normal((300, 21, 5)), "pobj": rng.standard_normal(300),
+              "exit": rng.integers(-3, 2, 300).astype(np.int32), "winners": rng.standard_normal((37, 11))}
+    rows = bench.dump_outputs(str(tmp_path / "all"), arrays)
+    assert rows == {"xtraj": 300, "pobj": 300, "exit": 300, "winners": 37}
+    for k, a in arrays.items():
+        got = np.load(tmp_path / "all" / (k + ".npy"))
+        assert got.dtype == np.float64 and np.array_equal(got, a)
+    budget = 100_000
+    rows = bench.dump_outputs(str(tmp_path / "a"), arrays, budget=budget)
+    bench.dump_outputs(str(tmp_path / "b"), arrays, budget=budget)
+    assert 0 < rows["xtraj"] == rows["pobj"] == rows["exit"] < 300 and 0 < rows["winners"] < 37
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= budget
+    for k in arrays:
+        assert (tmp_path / "a" / (k + ".npy")).read_bytes() == (tmp_path / "b" / (k + ".npy")).read_bytes()
+    # the sample is rows of the output, in order; arrays of one row count keep the same rows
+    x, p = np.load(tmp_path / "a" / "xtraj.npy"), np.load(tmp_path / "a" / "pobj.npy")
+    idx = [int(np.flatnonzero(arrays["pobj"] == v)[0]) for v in p]
+    assert idx == sorted(idx) and np.array_equal(x, arrays["xtraj"][idx])
+
+
+@pytest.mark.gpu
+def test_plain_run_times_its_steps_only_and_dumps_the_last_step(tmp_path):
+    """a plain `bench.py --gpus 1 --steps K --warmup W` prints the headline line without the legs that
+    take runs of their own (other QP profile, CPU baseline, oracle parity: --full), and
+    --dump-outputs writes the last timed step's outputs: finite float64 arrays of the batch's shapes
+    whose winner records are rows of the dumped solves"""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    d = tmp_path / "out"
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--scenes", "16",
+                        "--dump-outputs", str(d)], cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    line = json.loads(lines[0])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["unit"] == "solves/s" and line["dtype"] == "f64"
+    assert line["higher_is_better"] is True and line["ms_per_step"] > 0
+    # value = solves per second of the timed steps: 16 scenes x 8 guesses per step
+    assert abs(line["value"] * line["ms_per_step"] * 1e-3 / (16 * 8) - 1) < 1e-3
+    assert not {"qp_profile_alt", "cpu_baseline", "vs_cpu_baseline", "parity"} & set(line)
+    shapes = {"xtraj": (128, 21, 5), "utraj": (128, 20, 2), "pobj": (128,), "exit": (128,), "info": (128, 4)}
+    out = {f[:-4]: np.load(d / f) for f in os.listdir(d)}
+    assert set(out) == set(shapes) | {"winners"}
+    for k, a in out.items():
+        assert a.dtype == np.float64 and a.shape[0] in (16, 128)
+        assert k == "winners" or a.shape == shapes[k]
+    ok = out["exit"] == 1
+    assert ok.any() and np.isfinite(out["xtraj"][ok]).all() and np.isfinite(out["pobj"][ok]).all()
+    assert line["solver_stats"]["success_frac"] == ok.mean()
+    # winners: xtraj | utraj | pobj | planner index of the selected planner (index -1: planner 0's)
+    w = out["winners"]
+    assert w.shape == (16, 21 * 5 + 20 * 2 + 2)
+    pick = np.arange(16) * 8 + np.maximum(w[:, -1], 0).astype(int)
+    assert np.array_equal(w[:, :105], out["xtraj"][pick].reshape(16, -1), equal_nan=True)
+    assert np.array_equal(w[:, 105:145], out["utraj"][pick].reshape(16, -1), equal_nan=True)
+    assert np.array_equal(w[:, 145], out["pobj"][pick], equal_nan=True)
 
 
 def test_source_hash_tracks_kernel_sources():
