@@ -20,6 +20,10 @@ SOURCES = {"mpcg_kernels.hip": [], "mpcg_prepare.hip": ["-ffp-contract=off"],
            "mpcg_inst_tmpc20.hip": [], "mpcg_inst_tmpc30.hip": [], "mpcg_inst_shmpc.hip": [],
            "mpcg_inst_bicycle.hip": []}
 HEADERS = ["mpcg_device.h", "mpcg_sqp.h", "mpcg_sqp_body.inc", "mpcg_prepare.h", "mpcg_bicycle.h", "mpcg_instance.h"]
+# the multi-robot layer (include/mpcg_fleet.h): linked into libmpcg.so but kept out of SOURCES / HEADERS,
+# whose source_hash() is the identity the committed counter profiles (profiles/traffic_*.json) were taken on
+FLEET_SOURCES = {"mpcg_fleet.hip": ["-ffp-contract=off"]}
+FLEET_HEADERS = ["mpcg_fleet.h"]
 HOST_SOURCES = ["host/mpcg_yaml.cpp", "host/mpcg_solver.cpp"]
 HOST_HEADERS = ["mpc_planner_solver/mpcg_yaml.h", "mpc_planner_solver/mpcg_config.h", "mpc_planner_solver/state.h",
                 "mpc_planner_solver/mpcg_solver_interface.h", "mpc_planner_solver/solver_interface.h"]
@@ -53,7 +57,9 @@ def build_lib(force: bool = False, verbose: bool = False, extra_flags=(), out: s
     """libmpcg.so (or a diagnostic / variant build of it with extra_flags at `out`; `sources`
     restricts the built-in instance files of such a build)"""
     srcs = SOURCES if sources is None else {k: v for k, v in SOURCES.items() if k in sources}
-    deps = [os.path.join(CSRC, s) for s in list(SOURCES) + HEADERS] + [os.path.join(INCLUDE, "mpcg.h"), __file__]
+    srcs = {**srcs, **FLEET_SOURCES}
+    deps = [os.path.join(CSRC, s) for s in list(SOURCES) + HEADERS + list(FLEET_SOURCES) + FLEET_HEADERS] + \
+        [os.path.join(INCLUDE, "mpcg.h"), os.path.join(INCLUDE, "mpcg_fleet.h"), __file__]
     if not force and not _stale(out, deps):
         return out
     objdir = os.path.join(BUILD, "obj" + ("_" + "_".join(f.strip("-").replace("=", "") for f in extra_flags)

@@ -10,9 +10,9 @@ import os
 
 import numpy as np
 
-from .native_spec import (ABI_VERSION, DEFAULT_OPTIONS, EXPORTS, INFO_STRIDE, NU, NVAR, NX, STATS_STRIDE,  # noqa: F401
-                          UNICYCLE_LB, UNICYCLE_UB, MpcgIo, MpcgProblem, MpcgSceneIo, MpcgStepIo, MpcgScenarioIo,
-                          problem_from_layout)
+from .native_spec import (ABI_VERSION, DEFAULT_OPTIONS, EXPORTS, FLEET_EXPORTS, INFO_STRIDE, NU, NVAR, NX,  # noqa: F401
+                          STATS_STRIDE, UNICYCLE_LB, UNICYCLE_UB, MpcgFleetSettings, MpcgFleetState, MpcgIo,
+                          MpcgProblem, MpcgSceneIo, MpcgStepIo, MpcgScenarioIo, problem_from_layout)
 
 PKG = os.path.dirname(os.path.abspath(__file__))
 # MPCG_LIB selects a diagnostic build (e.g. libmpcg_stamps.so); default the production library
@@ -69,6 +69,12 @@ def _load():
     lib.mpcg_select_lowest_cost_device.restype = C.c_int
     lib.mpcg_winner_records_device.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]
     lib.mpcg_winner_records_device.restype = C.c_int
+    # include/mpcg_fleet.h
+    FS, FT = C.POINTER(MpcgFleetSettings), C.POINTER(MpcgFleetState)
+    lib.mpcg_fleet_obstacles.argtypes = [P, C.c_int, C.c_int, C.c_int, FS, FT, vp, vp, vp, vp, C.c_double, vp, vp, vp]
+    lib.mpcg_fleet_obstacles.restype = C.c_int
+    lib.mpcg_fleet_publish.argtypes = [P, C.c_int, C.c_int, C.c_int, FS, FT, vp, vp, vp, vp, vp, C.c_double, vp, vp, vp]
+    lib.mpcg_fleet_publish.restype = C.c_int
     # (MPCG_ABI_ACCEPT_OLDER, A/B timing runs of an earlier round's library only: ABI versions whose
     # mpcg_problem is a prefix of this one -- later ABIs only append fields)
     older = {int(v) for v in os.environ.get("MPCG_ABI_ACCEPT_OLDER", "").split(",") if v.strip().isdigit()}
@@ -403,3 +409,71 @@ def select_lowest_cost_device(n_scenes, n_solvers, pobj, exit_code, out=None, st
                                             C.c_void_p(s.cuda_stream))
     _check(rc, "mpcg_select_lowest_cost_device")
     return best
+
+
+def _fleet_state(fstate: dict, S: int, N: int) -> MpcgFleetState:
+    import torch
+
+    sp, stm, lst, pt = (fstate[k] for k in ("sent_plan", "sent_time", "last_send_time", "prev_topology"))
+    for t_, n in ((sp, S * N * 3), (stm, S), (lst, S)):
+        assert t_.dtype == torch.float64 and t_.is_cuda and t_.is_contiguous() and t_.numel() == n
+    assert pt.dtype == torch.int32 and pt.is_cuda and pt.is_contiguous() and pt.numel() == S
+    return MpcgFleetState(sp.data_ptr(), stm.data_ptr(), lst.data_ptr(), pt.data_ptr())
+
+
+def fleet_obstacles_device(pr: MpcgProblem, F: int, R: int, settings: MpcgFleetSettings, fstate: dict, state, now: float,
+                           obst, obst_meta, array_obst=None, array_meta=None, array_id=None, stream=None):
+    """mpcg_fleet_obstacles (include/mpcg_fleet.h): shift every sender's plan in `fstate`
+    (dict sent_plan (F, R, N, 3), sent_time, last_send_time (F, R) float64, prev_topology (F, R)
+    int32, device tensors, updated in place) to `now`, then write every robot's obstacle rows into
+    obst (S, n_ell, N, 5) / obst_meta (S, n_ell, 2), S = F * R.  array_obst (F, A, N, 5), array_meta
+    (F, A, 2), array_id (F, A) int32 or None: the fleets' non-communicating obstacles.
+    Asynchronous on `stream`; nothing is allocated."""
+    import torch
+
+    S, N = F * R, pr.N
+    A = 0 if array_obst is None else array_obst.shape[1]
+    assert tuple(state.shape) == (S, pr.nx) and state.dtype == torch.float64 and state.is_contiguous()
+    assert tuple(obst.shape) == (S, pr.n_ell, N, 5) and tuple(obst_meta.shape) == (S, pr.n_ell, 2)
+    for t_ in (obst, obst_meta):
+        assert t_.dtype == torch.float64 and t_.is_cuda and t_.is_contiguous()
+    if A:
+        assert tuple(array_obst.shape) == (F, A, N, 5) and tuple(array_meta.shape) == (F, A, 2)
+        for t_ in (array_obst, array_meta):
+            assert t_.dtype == torch.float64 and t_.is_cuda and t_.is_contiguous()
+        if array_id is not None:
+            assert tuple(array_id.shape) == (F, A) and array_id.dtype == torch.int32 and array_id.is_contiguous()
+    st = _fleet_state(fstate, S, N)
+    s = stream if stream is not None else torch.cuda.current_stream(state.device)
+    rc = lib.mpcg_fleet_obstacles(C.byref(pr), F, R, A, C.byref(settings), C.byref(st), _ptr(state),
+                                  _ptr(array_obst) if A else None, _ptr(array_meta) if A else None,
+                                  _ptr(array_id) if A else None, float(now), _ptr(obst), _ptr(obst_meta),
+                                  C.c_void_p(s.cuda_stream))
+    _check(rc, "mpcg_fleet_obstacles")
+
+
+def fleet_publish_device(pr: MpcgProblem, F: int, R: int, G: int, settings: MpcgFleetSettings, fstate: dict, best, xtraj,
+                         state, now: float, reason, published, topology=None, guided=None, stream=None):
+    """mpcg_fleet_publish (include/mpcg_fleet.h): after the solves of step `now`, every robot's
+    plan, selected topology and communication trigger; publishers' plans replace their entry of
+    `fstate` in place.  best (S,) int32, xtraj (S*G, N+1, nx), state (S, nx), topology (S, G) int32
+    or None, guided (S, G) uint8 or None; outputs reason (S,) int32, published (S,) uint8.
+    Asynchronous on `stream`; nothing is allocated."""
+    import torch
+
+    S, N = F * R, pr.N
+    assert best.dtype == torch.int32 and best.is_contiguous() and best.numel() == S
+    assert tuple(xtraj.shape) == (S * G, N + 1, pr.nx) and xtraj.dtype == torch.float64 and xtraj.is_contiguous()
+    assert tuple(state.shape) == (S, pr.nx) and state.dtype == torch.float64 and state.is_contiguous()
+    assert reason.dtype == torch.int32 and reason.is_contiguous() and reason.numel() == S
+    assert published.dtype == torch.uint8 and published.is_contiguous() and published.numel() == S
+    if topology is not None:
+        assert topology.dtype == torch.int32 and topology.is_contiguous() and topology.numel() == S * G
+    if guided is not None:
+        assert guided.dtype == torch.uint8 and guided.is_contiguous() and guided.numel() == S * G
+    st = _fleet_state(fstate, S, N)
+    s = stream if stream is not None else torch.cuda.current_stream(state.device)
+    rc = lib.mpcg_fleet_publish(C.byref(pr), F, R, G, C.byref(settings), C.byref(st), _ptr(best), _ptr(xtraj),
+                                _ptr(state), _ptr(topology), _ptr(guided), float(now), _ptr(reason), _ptr(published),
+                                C.c_void_p(s.cuda_stream))
+    _check(rc, "mpcg_fleet_publish")

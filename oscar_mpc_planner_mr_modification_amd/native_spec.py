@@ -163,3 +163,26 @@ EXPORTS = ("mpcg_abi_version", "mpcg_last_error", "mpcg_supported", "mpcg_num_h"
            "mpcg_instance_traits", "mpcg_problem_set_qp_profile")
 
 
+class MpcgFleetSettings(C.Structure):
+    """Mirror of `mpcg_fleet_settings` (include/mpcg_fleet.h)."""
+    _fields_ = [("control_frequency", C.c_double), ("v_max", C.c_double), ("w_max", C.c_double),
+                ("robot_obstacle_radius", C.c_double), ("probabilistic", C.c_int), ("chi_gaussian", C.c_double),
+                ("communicate_on_topology_switch_only", C.c_int), ("n_paths", C.c_int),
+                ("max_geometric_deviation", C.c_double), ("heartbeat_time", C.c_double),
+                ("deceleration", C.c_double)]
+
+
+class MpcgFleetState(C.Structure):
+    """Mirror of `mpcg_fleet_state` (include/mpcg_fleet.h)."""
+    _fields_ = [("sent_plan", C.c_void_p), ("sent_time", C.c_void_p), ("last_send_time", C.c_void_p),
+                ("prev_topology", C.c_void_p)]
+
+
+# the multi-robot layer (include/mpcg_fleet.h), exported from the same library; listed apart from
+# EXPORTS, which mirrors include/mpcg.h
+FLEET_EXPORTS = ("mpcg_fleet_obstacles", "mpcg_fleet_publish")
+# mpcg_fleet_publish's reason (CommunicationTriggerReason)
+FLEET_REASONS = {0: "NO_COMMUNICATION", 1: "INFEASIBLE", 3: "TOPOLOGY_CHANGE", 4: "GEOMETRIC", 5: "TIME",
+                 6: "NON_GUIDED_HOMOLOGY_FAIL"}
+
+
