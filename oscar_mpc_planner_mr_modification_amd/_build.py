@@ -115,6 +115,23 @@ def build_instance(layout, out_dir: str, force: bool = False) -> str:
     return so
 
 
+def build_stage_probe(force: bool = False) -> str:
+    """build/probe/libstage_probe.so: the test-only translation unit tests/cpp/stage_probe.hip
+    (single-thread kernels around the per-stage device functions of mpcg_device.h /
+    mpcg_bicycle.h, tests/test_gpu_stage_functions.py), compiled with the flags of the kernel
+    instances."""
+    src = os.path.join(ROOT, "tests", "cpp", "stage_probe.hip")
+    out_dir = os.path.join(BUILD, "probe")
+    so = os.path.join(out_dir, "libstage_probe.so")
+    deps = [src, os.path.join(INCLUDE, "mpcg.h"), __file__] + [os.path.join(CSRC, h) for h in HEADERS]
+    if force or _stale(so, deps):
+        os.makedirs(out_dir, exist_ok=True)
+        obj = _hipcc_obj(src, os.path.join(out_dir, "stage_probe.o"))
+        subprocess.run(["hipcc", f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", so + ".tmp", obj], check=True)
+        os.replace(so + ".tmp", so)
+    return so
+
+
 def build_cpp(config="C2", force: bool = False, verbose: bool = False) -> dict:
     """The drop-in C++ MPCPlanner::Solver for one generated solver
     (dimensions are compile-time, as in the reference): codegen into

@@ -206,3 +206,77 @@ def test_replayed_multi_robot_scene_through_the_gpu_step(oracle_mod):
     ok = ex == 1
     assert ok.any()
     assert np.abs(got["xtraj"].cpu().numpy()[ok] - ref["xtraj"][ok]).max() <= 1e-4
+
+
+@pytest.mark.gpu
+def test_replayed_scene_with_probabilistic_obstacles_through_the_gpu_step(oracle_mod):
+    """The same producer path with the reference's probabilistic mode: the array obstacles are
+    GAUSSIAN (unequal semi-axes along the horizon, non-zero angles -> rotated ellipsoid rows with
+    chi = ExponentialQuantile(0.5, 0.95)) and the disc sits 0.2 m ahead of the robot's centre.
+    GPU producer bit for bit against the host producer, GPU solve against the oracle under the
+    bars of tests/test_gpu_geometry.py (geometry_cases.compare_with_oracle)."""
+    import torch
+
+    import geometry_cases as gc
+    from oscar_mpc_planner_mr_modification_amd import native
+    from oscar_mpc_planner_mr_modification_amd.layouts import config_layout
+    from oscar_mpc_planner_mr_modification_amd.producers import prepare_host
+    from oscar_mpc_planner_mr_modification_amd.synthetic import (DECELERATION, ROBOT_RADIUS, SETTINGS_WEIGHTS,
+                                                                 make_scenes)
+    lay = config_layout("C4")
+    N, dt = lay.N, lay.dt
+    S, G = 3, 8
+    sc = make_scenes(lay, S, G, n_obs=lay.n_ell, seed=4711)
+    sc.stage_params[:, lay.idx("ego_disc_0_offset")] = 0.2
+    k = np.arange(N)
+    for s in range(S):
+        x0 = sc.state[s]
+        tr = ob.RobotObstacleTracker(["/jackal1", "/jackal2", "/jackal3", "/jackal4"], "/jackal1", 0.325, N, dt,
+                                     max_obstacles=lay.n_ell, probabilistic=True)
+        for r, ns in enumerate(("/jackal2", "/jackal3", "/jackal4")):
+            start = (x0[0] + 3.0 + r, x0[1] - 1.5 + 1.5 * r)
+            pos, ang = _line_plan(start[0], start[1], -0.4, 0.1 * (r - 1), N, dt)
+            tr.on_trajectory(ns, ob.direct_trajectory_msg(r + 1, (*start, ang[0]), pos, ang, dt, stamp=0.0), 0.0)
+        msgs = []
+        c, sn = math.cos(x0[2]), math.sin(x0[2])
+        for j in range(5):
+            # standing 6, 8, ... m ahead of the robot, 2 m to alternating sides of its heading: in the way
+            # of the plans, so that these rows are active (19 of 24 solves succeed, 18 with such a row)
+            ahead, lat = 6.0 + 2.0 * j, 2.0 if j % 2 else -2.0
+            px, py = x0[0] + ahead * c - lat * sn, x0[1] + ahead * sn + lat * c
+            pos, _ = _line_plan(px, py, 0.0, 0.0, N, dt)
+            ang = list(0.4 * (j + 1) + 0.03 * k)                              # non-zero, turning
+            major = list(0.05 * (j + 1) * np.sqrt(1.0 + k))                   # grows along the horizon
+            minor = list(0.4 * np.asarray(major))
+            msgs.append(ob.obstacle_gmm_msg(10 + j, px, py, ang[0], pos, ang, major=major, minor=minor))
+        arr = ob.obstacles_from_array({"obstacles": msgs}, 0.325, probabilistic=True)
+        assert all(o.prediction_type == ob.GAUSSIAN for o in arr)
+        lst = tr.prepare(arr, x0, now=0.13)
+        sc.obst[s], sc.obst_meta[s] = ob.scene_obstacle_arrays(lst, N)
+    chi = ob.exponential_quantile(0.5, 0.95)
+    assert (sc.obst_meta[:, :5, 1] == chi).all() and (sc.obst[:, :5, :, 3] > sc.obst[:, :5, :, 4]).all()
+    assert (np.abs(sc.obst[:, :5, :, 2]) > 0.01).all()
+    host = prepare_host(lay, sc, ROBOT_RADIUS, SETTINGS_WEIGHTS["consistency"], DECELERATION)
+    dev = torch.device("cuda:0")
+    pr = native.problem_from_layout(lay)
+    out = native.prepare_device(pr, native.scenes_to_device(sc, dev), ROBOT_RADIUS, SETTINGS_WEIGHTS["consistency"],
+                                DECELERATION)
+    res = native.solve_batch_device(pr, out["params"], out["warm"], out["xinit"], lam_out=True)
+    torch.cuda.synchronize()
+    prm, warm, xinit = (out[k_].cpu().numpy() for k_ in ("params", "warm", "xinit"))
+    np.testing.assert_array_equal(prm, host.params)
+    ix = lay.idx
+    assert (prm[:, :, ix("ego_disc_0_offset")] == 0.2).all()
+    assert (prm[:, 1:, ix("ellipsoid_obst_0_chi")] == chi).all() and (prm[:, 1:, ix("ellipsoid_obst_0_major")] > 0).all()
+    got = {k_: v.cpu().numpy() for k_, v in res.items()}
+    o, ol = oracle_mod.Oracle(lay), oracle_mod.Oracle(lay, literal=True)
+    ref = o.solve_batch(prm, warm, xinit, return_lam=True)
+    lit = ol.solve_batch(prm, warm, xinit, return_lam=True)
+    assert np.array_equal(ref["status"], lit["status"])
+    ok = ref["status"] == 1
+    # the Gaussian rows are active in the successful solves (else the comparison says nothing about them)
+    n_lam = lay.nx + lay.n_lin
+    assert ok.mean() >= 0.6
+    assert (np.abs(ref["lam"][ok][:, :, n_lam:n_lam + 5]) > 1e-6).any((1, 2)).mean() >= 1 / 3
+    gc.compare_with_oracle("C4 probabilistic replay", ref, lit, got, check_lam=True,
+                           scatter=lambda i: gc.oracle_scatter(lay, prm, warm, xinit, i))
