@@ -11,8 +11,9 @@ import os
 import numpy as np
 
 from .native_spec import (ABI_VERSION, DEFAULT_OPTIONS, EXPORTS, FLEET_EXPORTS, INFO_STRIDE, NU, NVAR, NX,  # noqa: F401
-                          STATS_STRIDE, UNICYCLE_LB, UNICYCLE_UB, MpcgFleetSettings, MpcgFleetState, MpcgIo,
-                          MpcgProblem, MpcgSceneIo, MpcgStepIo, MpcgScenarioIo, problem_from_layout)
+                          PATH_EXPORTS, STATS_STRIDE, UNICYCLE_LB, UNICYCLE_UB, MpcgFleetSettings, MpcgFleetState,
+                          MpcgIo, MpcgPathSettings, MpcgPathTable, MpcgProblem, MpcgSceneIo, MpcgStepIo,
+                          MpcgScenarioIo, problem_from_layout)
 
 PKG = os.path.dirname(os.path.abspath(__file__))
 # MPCG_LIB selects a diagnostic build (e.g. libmpcg_stamps.so); default the production library
@@ -75,6 +76,12 @@ def _load():
     lib.mpcg_fleet_obstacles.restype = C.c_int
     lib.mpcg_fleet_publish.argtypes = [P, C.c_int, C.c_int, C.c_int, FS, FT, vp, vp, vp, vp, vp, C.c_double, vp, vp, vp]
     lib.mpcg_fleet_publish.restype = C.c_int
+    # include/mpcg_path.h
+    lib.mpcg_path_update.argtypes = [P, C.c_int, C.POINTER(MpcgPathTable), vp, vp, vp, vp, vp, vp, vp]
+    lib.mpcg_path_update.restype = C.c_int
+    lib.mpcg_path_command.argtypes = [P, C.c_int, C.c_int, C.POINTER(MpcgPathSettings), vp, vp, vp, vp, vp, C.c_int,
+                                      vp, vp, vp]
+    lib.mpcg_path_command.restype = C.c_int
     # (MPCG_ABI_ACCEPT_OLDER, A/B timing runs of an earlier round's library only: ABI versions whose
     # mpcg_problem is a prefix of this one -- later ABIs only append fields)
     older = {int(v) for v in os.environ.get("MPCG_ABI_ACCEPT_OLDER", "").split(",") if v.strip().isdigit()}
@@ -477,3 +484,66 @@ def fleet_publish_device(pr: MpcgProblem, F: int, R: int, G: int, settings: Mpcg
                                 _ptr(state), _ptr(topology), _ptr(guided), float(now), _ptr(reason), _ptr(published),
                                 C.c_void_p(s.cuda_stream))
     _check(rc, "mpcg_fleet_publish")
+
+
+def path_table_device(table, path_of, device) -> dict:
+    """paths.PathTable + path_of (S,) -> the device tensors and the mpcg_path_table of
+    include/mpcg_path.h (dict coef, knots, n_segments, path_of, path_of_host, native)."""
+    import torch
+
+    coef = torch.from_numpy(np.ascontiguousarray(table.coef, np.float64)).to(device)
+    knots = torch.from_numpy(np.ascontiguousarray(table.knots, np.float64)).to(device)
+    nseg = torch.from_numpy(np.ascontiguousarray(table.n_segments, np.int32)).to(device)
+    po_host = np.ascontiguousarray(path_of, np.int32)
+    po = torch.from_numpy(po_host).to(device)
+    P, M = coef.shape[0], coef.shape[1]
+    assert tuple(coef.shape) == (P, M, 8) and tuple(knots.shape) == (P, M + 1) and tuple(nseg.shape) == (P,)
+    nat = MpcgPathTable(coef.data_ptr(), knots.data_ptr(), nseg.data_ptr(), po.data_ptr(), P, M)
+    return dict(coef=coef, knots=knots, n_segments=nseg, path_of=po, path_of_host=po_host, native=nat)
+
+
+def path_update_device(pr: MpcgProblem, dtable: dict, state, closest_segment, closest_s, stage_params, reached,
+                       stream=None):
+    """mpcg_path_update (include/mpcg_path.h): the closest point of every scene's state (S, nx) on its
+    path (`dtable`: path_table_device), closest_segment (S,) int32 in / out (-1: not initialised),
+    closest_s (S,) float64, the window of n_seg segments into stage_params (S, npar) and reached (S,)
+    uint8.  Asynchronous on `stream`; nothing is allocated."""
+    import torch
+
+    S = state.shape[0]
+    assert tuple(state.shape) == (S, pr.nx) and tuple(stage_params.shape) == (S, pr.npar)
+    for t_ in (state, closest_s, stage_params):
+        assert t_.dtype == torch.float64 and t_.is_cuda and t_.is_contiguous()
+    assert closest_segment.dtype == torch.int32 and closest_segment.is_contiguous() and closest_segment.numel() == S
+    assert closest_s.numel() == S and dtable["path_of"].numel() == S
+    assert reached.dtype == torch.uint8 and reached.is_contiguous() and reached.numel() == S
+    s = stream if stream is not None else torch.cuda.current_stream(state.device)
+    rc = lib.mpcg_path_update(C.byref(pr), S, C.byref(dtable["native"]), dtable["path_of_host"].ctypes.data,
+                              _ptr(state), _ptr(closest_segment), _ptr(closest_s), _ptr(stage_params), _ptr(reached),
+                              C.c_void_p(s.cuda_stream))
+    _check(rc, "mpcg_path_update")
+
+
+def path_command_device(pr: MpcgProblem, G: int, settings: MpcgPathSettings, best, xtraj, utraj, state, cmd,
+                        closest_s=None, spline_slot: int = -1, state_next=None, stream=None):
+    """mpcg_path_command (include/mpcg_path.h): cmd (S, 2) = (v, w) from best (S,) int32, the winner's
+    xtraj (S*G, N+1, nx) / utraj (S*G, N, nu) and state (S, nx); with settings.plant, state_next (S, nx)
+    from the kinematic stand-in plant, its entry spline_slot set to closest_s (S,).  Asynchronous on
+    `stream`; nothing is allocated."""
+    import torch
+
+    S, N = state.shape[0], pr.N
+    assert best.dtype == torch.int32 and best.is_contiguous() and best.numel() == S
+    assert tuple(xtraj.shape) == (S * G, N + 1, pr.nx) and tuple(utraj.shape) == (S * G, N, pr.nu)
+    assert tuple(state.shape) == (S, pr.nx) and tuple(cmd.shape) == (S, 2)
+    for t_ in (xtraj, utraj, state, cmd) + tuple(t_ for t_ in (closest_s, state_next) if t_ is not None):
+        assert t_.dtype == torch.float64 and t_.is_cuda and t_.is_contiguous()
+    if state_next is not None:
+        assert tuple(state_next.shape) == (S, pr.nx)
+    if closest_s is not None:
+        assert closest_s.numel() == S
+    s = stream if stream is not None else torch.cuda.current_stream(state.device)
+    rc = lib.mpcg_path_command(C.byref(pr), S, G, C.byref(settings), _ptr(best), _ptr(xtraj), _ptr(utraj), _ptr(state),
+                               _ptr(closest_s), int(spline_slot), _ptr(cmd), _ptr(state_next),
+                               C.c_void_p(s.cuda_stream))
+    _check(rc, "mpcg_path_command")

@@ -186,3 +186,18 @@ FLEET_REASONS = {0: "NO_COMMUNICATION", 1: "INFEASIBLE", 3: "TOPOLOGY_CHANGE", 4
                  6: "NON_GUIDED_HOMOLOGY_FAIL"}
 
 
+class MpcgPathTable(C.Structure):
+    """Mirror of `mpcg_path_table` (include/mpcg_path.h)."""
+    _fields_ = [("coef", C.c_void_p), ("knots", C.c_void_p), ("n_segments", C.c_void_p), ("path_of", C.c_void_p),
+                ("n_paths", C.c_int), ("max_segments", C.c_int)]
+
+
+class MpcgPathSettings(C.Structure):
+    """Mirror of `mpcg_path_settings` (include/mpcg_path.h)."""
+    _fields_ = [("control_frequency", C.c_double), ("deceleration", C.c_double), ("plant", C.c_int)]
+
+
+# the reference-path tracking (include/mpcg_path.h), exported from the same library
+PATH_EXPORTS = ("mpcg_path_update", "mpcg_path_command")
+PATH_MAX_SEGMENTS, PATH_SAMPLES, PATH_ROUNDS, PATH_REACHED_RADIUS = 64, 64, 5, 1.5
+
