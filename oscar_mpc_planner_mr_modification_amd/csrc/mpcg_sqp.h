@@ -253,6 +253,24 @@ struct Cfg {
 #else
     static constexpr bool REC_FLAT = CHAIN_SPLIT && (PARTS == 3 || MPCG_REC_P2);
 #endif
+    // RES_CARRY: the refinement test's pass (HPIPM's profile) evaluates H dz, F' pi and F dz + b - dz+ at the
+    // trial point dz + ddz on the stage blocks it has just read; the residual pass that follows evaluates
+    // the same products on the same blocks at dz + alpha ddz, and alpha is known before the test.  With the
+    // carry the test's pass forms both, and the residual pass after a test that asked for no refinement takes
+    // H dz, the stationarity rows' multiplier part and the dynamics residuals from it instead of reading the
+    // blocks again (mpcg_sqp_body.inc).  On the instances whose passes are split over the
+    // parts of a stage (RES_SPLIT: C1, C2, the N 10 shape); the single-owner instances (C4, C5, JS, JD, C3)
+    // are register-starved and keep their passes.
+    // Measured against the build without it (profiles/r07a_ab_parent_carry_C2_C1.jsonl, three alternating
+    // repetitions, every output of both bench batches bit for bit the same, profiles/r07a_bitcmp_*.jsonl):
+    // C2 14.80 -> 14.58 ms, C1 12.88 -> 12.56; the lean HPIPM kernels stay scratch-free (C2 497 -> 511
+    // of 512 registers per lane), the FULL variants spill a little more (C2 120 -> 156 B/lane, C1 0 -> 12;
+    // profiles/r07a_kernel_resources*.txt).  (MPCG_RES_CARRY=0: the passes without it, A/B and
+    // scripts/bitcmp.py)
+#ifndef MPCG_RES_CARRY
+#define MPCG_RES_CARRY 1
+#endif
+    static constexpr bool RES_CARRY = MPCG_RES_CARRY > 0 && MODEL_ == 0 && PARTS == 3 && NX_ == 5;
     // the capsule's QP memory (mpcg_io.qp_in / qp_out, opaque): per slot and lane the row's
     // slack then multiplier ([2 s + {0, 1}][64 lanes]), then the QP step [N+1][NZ] and the
     // dynamics multipliers [N][NX]

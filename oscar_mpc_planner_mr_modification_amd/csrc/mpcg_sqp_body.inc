@@ -44,6 +44,9 @@
                                ((PARTS == 3 && NX == 5) || MPCG_RES_SPLIT > 1);
     constexpr int DRS = (NX + PARTS - 1) / PARTS;  // dynamics rows per part
     static_assert(!(RES_SPLIT && LEAN), "the split passes read the dynamics multipliers from S.pin");
+    // the next iterate's residual products formed in the refinement test's pass (C::RES_CARRY, mpcg_sqp.h):
+    // the split passes only
+    constexpr bool RES_CARRY = C::RES_CARRY && RES_SPLIT && !LEAN && MPCG_ITREF > 0;
     // the centring pass of the conditional predictor-corrector (qp_cond_pred_corr) reads the predictor
     // products R.pr as zero through its flag instead of clearing them: a definition of the row state on
     // the way back around the phase loop costs the allocation.  Measured (profiles/r05o_ab.jsonl, bit for
@@ -255,6 +258,10 @@
         for (int j = 0; j < NZ; ++j) a += Fat(kq, i, j) * S.dz[kq][j];
         return a;
     };
+    // the iterate's move x + alpha dx of the update pass: RES_CARRY's test pass forms the next iterate ahead
+    // of it through the same expression, so that both round (contract) the same way and the carried values
+    // are the bits the residual pass would compute from the stored iterate
+    auto stepped = [](double x, double a, double dx) -> double { return x + a * dx; };
     Rows<C> R;
 #pragma unroll
     for (int r = 0; r < HS; ++r)
@@ -741,6 +748,16 @@
         int qstat = AC_MAXITER, qit = 0;
         double pinr[LEAN ? NX : 1];  // LEAN: the new dynamics multipliers of the own stage
         double Hdz[RES_SPLIT ? BVS : NZ];  // H_k dz_k of the current iterate: part 0 (RES_SPLIT: the lane's variables)
+        // RES_CARRY: the refinement test's pass hands the next residual pass H dz of the next iterate in Hdz,
+        // per owned variable its H dz + g + F' piq - piq- in S.q (dead between the last chain pass and the
+        // residual pass's own write; read back by the lane that wrote it) and its dynamics residuals in
+        // S.rdyn, where they belong.  Kept in registers instead, the three stationarity values and the
+        // residuals' maximum moved C2's allocation into scratch (0 -> 64 B/lane).  `carried` (wave-uniform)
+        // holds only from a test that asked for no refinement to the residual pass after it: it is clear at
+        // every QP start, the residual pass clears it, and no other pass of the phase loop sets it, so a
+        // centring or refinement redo and an untested final direction (the refinement cap) leave it clear.
+        // It is defined here, inside the solve, and nothing lane-dependent is added to the loop's back edge
+        bool carried = false;
         for (;; ++qit) {
             if constexpr (C::RELOAD_PARAMS) asm volatile("" : "+v"(pk));
             // ---- residuals
@@ -866,7 +883,37 @@
                         for (int i = 0; i < NBT; ++i) S.dH[k][NZ + i] = ab[i];
                     }
                     wave_sync();
-                    if (k <= N) {
+                    if (RES_CARRY && carried) {
+                        // the products of this iterate came with the refinement test (same operands, same
+                        // operation order: Hdz, S.q, S.rdyn and re are the bits of the pass below; S.q holds
+                        // the stationarity row without its box and h-row sums until its own value replaces
+                        // it).  Only rr is reassociated -- the fresh box and h-row sum is added last instead
+                        // of before the F' pi terms -- and may differ in the last bit; it feeds rs alone (the
+                        // exit tests and the refinement test's bound)
+                        if (k <= N) {
+#pragma unroll
+                            for (int j = 0; j < BVS; ++j) {
+                                const int v = LR.var(j);
+                                if (v >= NZ) continue;
+                                const int bi = C::blk(v);
+                                double rbox = rbj[j];
+                                if (bi >= 0) rbox += S.bx[k][bi];
+                                double qv = Hdz[j] + S.g[k][v] + qbj[j];
+                                if (bi >= 0) qv += S.bx[k][NB + bi];
+                                const double rr = S.q[k][v] + rbox;
+                                const bool free_var = (k == N) ? (v >= NU) : ((k == 0) ? (v < NU) : true);
+                                S.q[k][v] = qv;
+                                if (free_var) rs = fmax(rs, fabs(rr));
+                            }
+                            if (k < N) {
+#pragma unroll
+                                for (int jd = 0; jd < DRS; ++jd) {
+                                    const int i = part + PARTS * jd;
+                                    if (i < NX) re = fmax(re, fabs(S.rdyn[k][i]));
+                                }
+                            }
+                        }
+                    } else if (k <= N) {
                         double pq[NX];
 #pragma unroll
                         for (int m = 0; m < NX; ++m) pq[m] = k < N ? S.piq[k][m] : 0.0;
@@ -983,6 +1030,7 @@
             if (itref_on) cmx = wave_max(cmx);
             comp = wave_sum(comp);
             hcold = false;
+            carried = false;  // (consumed; only a refinement test that ends the phase loop sets it again)
             const double mu = comp / C::M_TOTAL;
 #ifdef MPCG_TRACE
             // diagnostic build only (scripts/trace_solve.py): the oracle's ORC_DEBUG line of solve
@@ -2219,25 +2267,67 @@
                                     for (int i = 0; i < NB; ++i) S.bx[k][i] = ra[i];
                                 }
                                 wave_sync();
+                                // RES_CARRY: next to the trial point dz + ddz, the next iterate dz + alpha ddz,
+                                // piq + alpha (pin - piq) (the update pass's expressions; alpha as below, from
+                                // amax alone) and its H dz, stationarity rows without the box and h-row sums, and
+                                // dynamics residuals, on the entries of H, [B A], g and b this pass reads anyway.
+                                // Hdz's old value is dead (no barrier pass follows a test in this iteration), and
+                                // so are S.q and S.rdyn (the chains are done; a refinement that follows
+                                // overwrites both)
+                                double an = 0.995 * amax;
+                                if (an > 1.0) an = 1.0;
                                 if (k <= N) {
-                                    double zt[NZ];
+                                    double zt[NZ], zn[RES_CARRY ? NZ : 1], pn[RES_CARRY ? NX : 1];
 #pragma unroll
-                                    for (int i = 0; i < NZ; ++i) zt[i] = S.dz[k][i] + S.ddz[k][i];
+                                    for (int i = 0; i < NZ; ++i) {
+                                        const double d = S.dz[k][i], dd = S.ddz[k][i];
+                                        zt[i] = d + dd;
+                                        if constexpr (RES_CARRY) zn[i] = stepped(d, an, dd);
+                                    }
+                                    if constexpr (RES_CARRY) {
+                                        if (k < N) {
+#pragma unroll
+                                            for (int m = 0; m < NX; ++m) {
+                                                const double p = S.piq[k][m];
+                                                pn[m] = stepped(p, an, S.pin[k][m] - p);
+                                            }
+                                        }
+                                    }
 #pragma unroll
                                     for (int j = 0; j < BVS; ++j) {
                                         const int v = LR.var(j);
                                         if (v >= NZ) continue;
-                                        double a = 0.0;
+                                        double a = 0.0, a2 = 0.0;
 #pragma unroll
-                                        for (int jj = 0; jj < NZ; ++jj) a += Hat(k, v, jj) * zt[jj];
-                                        double r = a + S.g[k][v] + rbq[j];
+                                        for (int jj = 0; jj < NZ; ++jj) {
+                                            const double h = Hat(k, v, jj);
+                                            a += h * zt[jj];
+                                            if constexpr (RES_CARRY) a2 += h * zn[jj];
+                                        }
+                                        const double gv = S.g[k][v];
+                                        double r = a + gv + rbq[j];
+                                        double c = a2 + gv;
                                         const int bi = C::blk(v);
                                         if (bi >= 0) r += S.bx[k][bi];
                                         if (k < N) {
 #pragma unroll
-                                            for (int m = 0; m < NX; ++m) r += Fat(k, m, v) * S.pin[k][m];
+                                            for (int m = 0; m < NX; ++m) {
+                                                const double f = Fat(k, m, v);
+                                                r += f * S.pin[k][m];
+                                                if constexpr (RES_CARRY) c += f * pn[m];
+                                            }
                                         }
-                                        if (k > 0 && v >= NU) r -= S.pin[k - 1][v - NU];
+                                        if (k > 0 && v >= NU) {
+                                            r -= S.pin[k - 1][v - NU];
+                                            if constexpr (RES_CARRY) {
+                                                const double p = S.piq[k - 1][v - NU];
+                                                c -= stepped(p, an, S.pin[k - 1][v - NU] - p);
+                                            }
+                                        }
+                                        if constexpr (RES_CARRY) {
+                                            Hdz[j] = a2;
+                                            S.q[k][v] = c;
+                                        }
                                         const bool free_var = (k == N) ? (v >= NU) : ((k == 0) ? (v < NU) : true);
                                         if (free_var) fail = fail || !(fabs(r) < thg);
                                     }
@@ -2246,10 +2336,17 @@
                                         for (int jd = 0; jd < DRS; ++jd) {
                                             const int i = part + PARTS * jd;
                                             if (i >= NX) continue;
-                                            double a = S.b[k][i] - (S.dz[k + 1][NU + i] + S.ddz[k + 1][NU + i]);
+                                            const double d = S.dz[k + 1][NU + i], dd = S.ddz[k + 1][NU + i];
+                                            double a = S.b[k][i] - (d + dd);
+                                            double a2 = S.b[k][i] - (RES_CARRY ? stepped(d, an, dd) : 0.0);
 #pragma unroll
-                                            for (int jj = 0; jj < NZ; ++jj) a += Fat(k, i, jj) * zt[jj];
+                                            for (int jj = 0; jj < NZ; ++jj) {
+                                                const double f = Fat(k, i, jj);
+                                                a += f * zt[jj];
+                                                if constexpr (RES_CARRY) a2 += f * zn[jj];
+                                            }
                                             fail = fail || !(fabs(a) < thb);
+                                            if constexpr (RES_CARRY) S.rdyn[k][i] = a2;
                                         }
                                     }
                                 }
@@ -2305,6 +2402,9 @@
                                 }
                             }
                             refine_now = __any(fail);
+                            // the direction stands: the phase loop ends here and the update pass moves the
+                            // iterate to the point the carry was formed at
+                            if constexpr (RES_CARRY) carried = !refine_now;
                             wave_sync();
                         }
                         STAMP_LAP(22);
@@ -2465,13 +2565,16 @@
 #pragma unroll
                     for (int j = 0; j < BVS; ++j) {
                         const int v = LR.var(j);
-                        if (v < NZ) S.dz[k][v] += alpha * S.ddz[k][v];
+                        if (v < NZ) S.dz[k][v] = stepped(S.dz[k][v], alpha, S.ddz[k][v]);
                     }
                     if (k < N) {
 #pragma unroll
                         for (int jd = 0; jd < DRS; ++jd) {
                             const int i = part + PARTS * jd;
-                            if (i < NX) S.piq[k][i] += alpha * (S.pin[k][i] - S.piq[k][i]);
+                            if (i < NX) {
+                                const double p = S.piq[k][i];
+                                S.piq[k][i] = stepped(p, alpha, S.pin[k][i] - p);
+                            }
                         }
                     }
                 }
