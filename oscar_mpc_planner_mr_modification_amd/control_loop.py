@@ -21,7 +21,7 @@ class ControlLoop:
     def __init__(self, layout: Layout, scenes, device, robot_radius: float, w_consistency: float,
                  selection_weight: float, deceleration: float = 3.0, shift_forward: bool = False,
                  consistency_on_non_guided: bool = True, elapsed: float | None = None,
-                 warmstart_with_mpc_solution: bool = False):
+                 warmstart_with_mpc_solution: bool = False, guidance_layer=None):
         import torch
 
         self.lay = layout
@@ -39,6 +39,9 @@ class ControlLoop:
         self.lam = torch.zeros((self.S * self.G, layout.N, LS), dtype=torch.float64, device=device)
         self.last = None
         self.existing = None
+        # guidance.GuidanceLayer or None: with a layer, guidance, existing_guidance and the class-keyed
+        # selection flags of every step come from mpcg_guidance_update instead of from outside
+        self.guidance_layer = guidance_layer
 
     def set_scene_data(self, state, obst, guidance, existing_guidance=None):
         """Replace the externally provided scene data (device tensors or arrays).
@@ -62,13 +65,20 @@ class ControlLoop:
     def step(self, stream=None):
         """One control step of every scene.  Returns dict(best, exit, xtraj, utraj, pobj, objective, prepared)."""
         pr, S, G, N = self.pr, self.S, self.G, self.lay.N
+        gl = self.guidance_layer
+        if gl is not None:
+            gl.update(self, stream=stream)
         if self.own_warm and self.last is not None:
             self.dsc["planner_xtraj"], self.dsc["planner_utraj"] = self.last["xtraj"], self.last["utraj"]
             self.dsc["existing_guidance"] = self.dsc["guided"] if self.existing is None else self.existing
+            if gl is not None:
+                self.dsc["existing_guidance"] = gl.existing_guidance
         prep = native.prepare_device(pr, self.dsc, self.rr, self.wc, self.dec, stream=stream,
                                      warmstart_with_mpc_solution=self.own_warm, shift_forward=self.shift)
         out = native.solve_batch_device(pr, prep["params"], prep["warm"], prep["xinit"], stream=stream,
                                         lam_in=self.lam, lam_out=True)
+        if gl is not None:
+            gl.mask(out["exit"], stream=stream)
         best, objective = native.select_best_device(S, G, N, out["xtraj"], out["pobj"], out["exit"],
                                                     prev_traj=prep["prev_interp"], w_cons=self.wc,
                                                     consistency_enabled=prep["consistency_active"],
@@ -76,6 +86,8 @@ class ControlLoop:
                                                     selection_weight=self.sw, stream=stream)
         self.last = dict(best=best, exit=out["exit"], xtraj=out["xtraj"], utraj=out["utraj"], pobj=out["pobj"],
                          objective=objective, prepared=prep, lam=out["lam"])
+        if gl is not None:
+            gl.after_select(self, self.last, stream=stream)
         return self.last
 
     def advance(self, state_next, stream=None):

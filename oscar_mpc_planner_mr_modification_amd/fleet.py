@@ -267,7 +267,8 @@ class FleetLoop:
 
     def step(self, now: float, topology=None, stream=None):
         """One control step of every robot at time `now`.  topology (S, G) int32 device tensor: the
-        topology id of every planner (None: planner index / 2 n_paths for the non-guided one).
+        topology id of every planner (None: the loop's guidance layer's class ids, or without a layer the
+        planner index / 2 n_paths for the non-guided one).
         Returns ControlLoop.step's dict plus reason (S,) int32 and published (S,) uint8."""
         from . import native
 
@@ -276,6 +277,8 @@ class FleetLoop:
                                       lp.dsc["obst"], lp.dsc["obst_meta"], self.array_obst, self.array_meta,
                                       self.array_id, stream=stream)
         out = lp.step(stream=stream)
+        if topology is None and lp.guidance_layer is not None:
+            topology = lp.guidance_layer.topology
         native.fleet_publish_device(lp.pr, self.F, self.R, lp.G, self._set, self.state, out["best"], out["xtraj"],
                                     lp.dsc["state"], now, self.reason, self.published, topology=topology,
                                     guided=lp.dsc["guided"], stream=stream)

@@ -10,10 +10,11 @@ import os
 
 import numpy as np
 
-from .native_spec import (ABI_VERSION, DEFAULT_OPTIONS, EXPORTS, FLEET_EXPORTS, INFO_STRIDE, NU, NVAR, NX,  # noqa: F401
-                          PATH_EXPORTS, STATS_STRIDE, UNICYCLE_LB, UNICYCLE_UB, MpcgFleetSettings, MpcgFleetState,
-                          MpcgIo, MpcgPathSettings, MpcgPathTable, MpcgProblem, MpcgSceneIo, MpcgStepIo,
-                          MpcgScenarioIo, problem_from_layout)
+from .native_spec import (ABI_VERSION, DEFAULT_OPTIONS, EXPORTS, FLEET_EXPORTS, GUIDANCE_CANDIDATES,  # noqa: F401
+                          GUIDANCE_EXPORTS, INFO_STRIDE, NU, NVAR, NX, PATH_EXPORTS, STATS_STRIDE, UNICYCLE_LB,
+                          UNICYCLE_UB, MpcgFleetSettings, MpcgFleetState, MpcgGuidanceOut, MpcgGuidanceSettings,
+                          MpcgGuidanceState, MpcgIo, MpcgPathSettings, MpcgPathTable, MpcgProblem, MpcgSceneIo,
+                          MpcgStepIo, MpcgScenarioIo, problem_from_layout)
 
 PKG = os.path.dirname(os.path.abspath(__file__))
 # MPCG_LIB selects a diagnostic build (e.g. libmpcg_stamps.so); default the production library
@@ -82,6 +83,14 @@ def _load():
     lib.mpcg_path_command.argtypes = [P, C.c_int, C.c_int, C.POINTER(MpcgPathSettings), vp, vp, vp, vp, vp, C.c_int,
                                       vp, vp, vp]
     lib.mpcg_path_command.restype = C.c_int
+    # include/mpcg_guidance.h
+    lib.mpcg_guidance_update.argtypes = [P, C.c_int, C.c_int, C.POINTER(MpcgGuidanceSettings), vp, vp, vp, vp,
+                                         C.POINTER(MpcgGuidanceState), C.POINTER(MpcgGuidanceOut), vp]
+    lib.mpcg_guidance_update.restype = C.c_int
+    lib.mpcg_guidance_mask.argtypes = [C.c_int, C.c_int, vp, vp, vp]
+    lib.mpcg_guidance_mask.restype = C.c_int
+    lib.mpcg_guidance_select.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, C.POINTER(MpcgGuidanceState), vp]
+    lib.mpcg_guidance_select.restype = C.c_int
     # (MPCG_ABI_ACCEPT_OLDER, A/B timing runs of an earlier round's library only: ABI versions whose
     # mpcg_problem is a prefix of this one -- later ABIs only append fields)
     older = {int(v) for v in os.environ.get("MPCG_ABI_ACCEPT_OLDER", "").split(",") if v.strip().isdigit()}
@@ -547,3 +556,78 @@ def path_command_device(pr: MpcgProblem, G: int, settings: MpcgPathSettings, bes
                                _ptr(closest_s), int(spline_slot), _ptr(cmd), _ptr(state_next),
                                C.c_void_p(s.cuda_stream))
     _check(rc, "mpcg_path_command")
+
+
+def _guidance_state(gstate: dict, S: int, G: int, N: int) -> MpcgGuidanceState:
+    import torch
+
+    K = 2 * (G - 1)
+    ct, cu, pc, sel, orig = (gstate[k] for k in ("class_traj", "class_used", "planner_class", "selected_topology",
+                                                 "prev_was_original"))
+    for t_, dt_, n in ((ct, torch.float64, S * K * (N + 1) * 2), (cu, torch.uint8, S * K), (pc, torch.int32, S * G),
+                       (sel, torch.int32, S), (orig, torch.uint8, S)):
+        assert t_.dtype == dt_ and t_.is_cuda and t_.is_contiguous() and t_.numel() == n
+    return MpcgGuidanceState(ct.data_ptr(), cu.data_ptr(), pc.data_ptr(), sel.data_ptr(), orig.data_ptr())
+
+
+def guidance_update_device(pr: MpcgProblem, S: int, G: int, settings: MpcgGuidanceSettings, state, stage_params, obst,
+                           obst_meta, gstate: dict, guidance, existing_guidance, previously_selected, consistency_on,
+                           topology, enabled, n_found, heading, sig_mask, sig_side, clearance, cost, stream=None):
+    """mpcg_guidance_update (include/mpcg_guidance.h): this step's guidance trajectories, class ids and
+    planner bookkeeping of S scenes x G planners from state (S, nx), stage_params (S, npar), obst
+    (S, n_ell, N, 5), obst_meta (S, n_ell, 2) and the layer state `gstate` (dict class_traj
+    (S, 2 (G - 1), N+1, 2), class_used (S, 2 (G - 1)) uint8, planner_class (S, G) int32, selected_topology
+    (S,) int32, prev_was_original (S,) uint8; class_traj / class_used updated in place).  Outputs:
+    guidance (S, G, N+1, 4), existing_guidance / previously_selected / consistency_on / enabled (S, G)
+    uint8, topology (S, G) int32, n_found (S,) int32, heading (S, 2), sig_mask / sig_side (S, G) int32,
+    clearance / cost (S, 8).  Asynchronous on `stream`; nothing is allocated."""
+    import torch
+
+    N = pr.N
+    assert tuple(state.shape) == (S, pr.nx) and tuple(stage_params.shape) == (S, pr.npar)
+    assert tuple(obst.shape) == (S, pr.n_ell, N, 5) and tuple(obst_meta.shape) == (S, pr.n_ell, 2)
+    assert tuple(guidance.shape) == (S, G, N + 1, 4) and tuple(heading.shape) == (S, 2)
+    assert tuple(clearance.shape) == (S, GUIDANCE_CANDIDATES) and tuple(cost.shape) == (S, GUIDANCE_CANDIDATES)
+    for t_ in (state, stage_params, obst, obst_meta, guidance, heading, clearance, cost):
+        assert t_.dtype == torch.float64 and t_.is_cuda and t_.is_contiguous()
+    for t_ in (existing_guidance, previously_selected, consistency_on, enabled):
+        assert t_.dtype == torch.uint8 and t_.is_cuda and t_.is_contiguous() and t_.numel() == S * G
+    for t_ in (topology, sig_mask, sig_side):
+        assert t_.dtype == torch.int32 and t_.is_cuda and t_.is_contiguous() and t_.numel() == S * G
+    assert n_found.dtype == torch.int32 and n_found.is_contiguous() and n_found.numel() == S
+    st = _guidance_state(gstate, S, G, N)
+    out = MpcgGuidanceOut(*(t_.data_ptr() for t_ in (guidance, existing_guidance, previously_selected, consistency_on,
+                                                     topology, enabled, n_found, heading, sig_mask, sig_side,
+                                                     clearance, cost)))
+    s = stream if stream is not None else torch.cuda.current_stream(state.device)
+    rc = lib.mpcg_guidance_update(C.byref(pr), S, G, C.byref(settings), _ptr(state), _ptr(stage_params), _ptr(obst),
+                                  _ptr(obst_meta), C.byref(st), C.byref(out), C.c_void_p(s.cuda_stream))
+    _check(rc, "mpcg_guidance_update")
+
+
+def guidance_mask_device(S: int, G: int, enabled, exit_code, stream=None):
+    """mpcg_guidance_mask: exit_code (S*G,) int32 of the planners with enabled (S, G) 0 becomes
+    MPCG_GUIDANCE_EXIT_DISABLED, in place."""
+    import torch
+
+    assert enabled.dtype == torch.uint8 and enabled.is_contiguous() and enabled.numel() == S * G
+    assert exit_code.dtype == torch.int32 and exit_code.is_contiguous() and exit_code.numel() == S * G
+    s = stream if stream is not None else torch.cuda.current_stream(exit_code.device)
+    _check(lib.mpcg_guidance_mask(S, G, _ptr(enabled), _ptr(exit_code), C.c_void_p(s.cuda_stream)),
+           "mpcg_guidance_mask")
+
+
+def guidance_select_device(S: int, G: int, best, guided, topology, enabled, gstate: dict, stream=None):
+    """mpcg_guidance_select: selected_topology, prev_was_original and planner_class of `gstate` from
+    best (S,) int32, guided / enabled (S, G) uint8 and topology (S, G) int32."""
+    import torch
+
+    assert best.dtype == torch.int32 and best.is_contiguous() and best.numel() == S
+    for t_ in (guided, enabled):
+        assert t_.dtype == torch.uint8 and t_.is_contiguous() and t_.numel() == S * G
+    assert topology.dtype == torch.int32 and topology.is_contiguous() and topology.numel() == S * G
+    N = gstate["class_traj"].shape[2] - 1
+    st = _guidance_state(gstate, S, G, N)
+    s = stream if stream is not None else torch.cuda.current_stream(best.device)
+    _check(lib.mpcg_guidance_select(S, G, _ptr(best), _ptr(guided), _ptr(topology), _ptr(enabled), C.byref(st),
+                                    C.c_void_p(s.cuda_stream)), "mpcg_guidance_select")

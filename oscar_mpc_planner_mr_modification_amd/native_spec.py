@@ -201,3 +201,31 @@ class MpcgPathSettings(C.Structure):
 PATH_EXPORTS = ("mpcg_path_update", "mpcg_path_command")
 PATH_MAX_SEGMENTS, PATH_SAMPLES, PATH_ROUNDS, PATH_REACHED_RADIUS = 64, 64, 5, 1.5
 
+
+
+class MpcgGuidanceSettings(C.Structure):
+    """Mirror of `mpcg_guidance_settings` (include/mpcg_guidance.h)."""
+    _fields_ = [("robot_radius", C.c_double), ("v_ref", C.c_double), ("consistency_on_non_guided", C.c_int)]
+
+
+class MpcgGuidanceState(C.Structure):
+    """Mirror of `mpcg_guidance_state` (include/mpcg_guidance.h)."""
+    _fields_ = [("class_traj", C.c_void_p), ("class_used", C.c_void_p), ("planner_class", C.c_void_p),
+                ("selected_topology", C.c_void_p), ("prev_was_original", C.c_void_p)]
+
+
+class MpcgGuidanceOut(C.Structure):
+    """Mirror of `mpcg_guidance_out` (include/mpcg_guidance.h)."""
+    _fields_ = [("guidance", C.c_void_p), ("existing_guidance", C.c_void_p), ("previously_selected", C.c_void_p),
+                ("consistency_on", C.c_void_p), ("topology", C.c_void_p), ("enabled", C.c_void_p),
+                ("n_found", C.c_void_p), ("heading", C.c_void_p), ("sig_mask", C.c_void_p), ("sig_side", C.c_void_p),
+                ("clearance", C.c_void_p), ("cost", C.c_void_p)]
+
+
+# the guidance layer (include/mpcg_guidance.h), exported from the same library
+GUIDANCE_EXPORTS = ("mpcg_guidance_update", "mpcg_guidance_mask", "mpcg_guidance_select")
+GUIDANCE_CANDIDATES, GUIDANCE_BITS, GUIDANCE_FINE, GUIDANCE_SWEEPS = 8, 3, 4, 4
+GUIDANCE_MAX_N, GUIDANCE_MAX_ELL, GUIDANCE_MAX_SEG = 32, 32, 8
+GUIDANCE_ACCEL, GUIDANCE_RELEVANT, GUIDANCE_OFFSET, GUIDANCE_WIDTH, GUIDANCE_ONSET = 1.0, 2.5, 1.2, 2.0, 0.8
+GUIDANCE_PUSH_MARGIN, GUIDANCE_CLEARANCE, GUIDANCE_V_FLOOR = 0.75, 0.25, 1e-3
+GUIDANCE_EXIT_DISABLED = -100

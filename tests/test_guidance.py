@@ -1,0 +1,427 @@
+"""The guidance layer on the host (guidance.guidance_update_host, map_planners_host,
+planner_flags_host, select_host) and the argument checks of its C ABI (include/mpcg_guidance.h).
+The kernels are compared with these restatements in tests/test_gpu_guidance.py."""
+import ctypes as C
+import inspect
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import guidance_cases as gc
+from oscar_mpc_planner_mr_modification_amd import guidance as gd
+from oscar_mpc_planner_mr_modification_amd import native_spec as ns
+from oscar_mpc_planner_mr_modification_amd.layouts import config_layout
+from oscar_mpc_planner_mr_modification_amd.synthetic import OBSTACLE_RADIUS, ROBOT_RADIUS
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HDR = os.path.join(ROOT, "include", "mpcg_guidance.h")
+LIB = os.path.join(ROOT, "oscar_mpc_planner_mr_modification_amd", "libmpcg.so")
+G = 8
+LAY = config_layout("C2")
+
+
+@pytest.fixture(scope="module")
+def first():
+    """The first update of the six scenes of gc.update_case, computed once and left unchanged."""
+    state, sp, ob, me = gc.update_case(LAY, 0)
+    st = gd.initial_state(len(state), G, LAY.N)
+    gdn = np.full((len(state), G, LAY.N + 1, 4), -7.0)
+    out = gd.guidance_update_host(LAY, state, sp, ob, me, st, gdn, G, gc.SETTINGS, details=True)
+    return dict(state=state, sp=sp, ob=ob, me=me, st=st, out=out)
+
+
+def scene_of(name):
+    return gc.SCENE_NAMES.index(name)
+
+
+def test_layout_of_the_cases():
+    assert (LAY.N, LAY.n_ell, LAY.nx) == (20, 8, 5) and LAY.n_seg <= ns.GUIDANCE_MAX_SEG
+
+
+def test_one_obstacle_dead_ahead(first):
+    s, out = scene_of("ahead"), first["out"]
+    d = out["details"][s]
+    N, dt = LAY.N, LAY.dt
+    nf = int(out["n_found"][s])
+    assert nf >= 2
+    sides = {int(out["sig_side"][s, p]) & 1 for p in range(nf)}
+    assert sides == {0, 1} and all(int(out["sig_mask"][s, p]) == 1 for p in range(nf))
+    required = ROBOT_RADIUS + OBSTACLE_RADIUS + ns.GUIDANCE_CLEARANCE
+    for p in range(nf):
+        g = out["guidance"][s, p]
+        np.testing.assert_array_equal(g[0, 0:2], first["state"][s, 0:2])
+        c = d["order"][p]
+        # exact: infeasible candidates are dropped by construction
+        assert d["clearance"][c] >= ns.GUIDANCE_CLEARANCE
+        # ... and the clearance is what it says: the distance to the obstacle at (k - 1) dt and k dt
+        dist = np.sqrt(((g[1:, 0:2] - first["ob"][s, 0, 0, 0:2]) ** 2).sum(-1)).min()
+        assert dist >= required - 1e-12
+        speed = np.sqrt((g[:, 2:4] ** 2).sum(-1))
+        assert np.abs(np.diff(speed)).max() <= 2.0 * dt + 1e-12
+        h = g[:, 2:4] / speed[:, None]
+        turn = np.arcsin(np.clip(np.abs(h[:-1, 0] * h[1:, 1] - h[:-1, 1] * h[1:, 0]), 0.0, 1.0))
+        assert turn.max() <= 0.8 * dt + 1e-12
+    # the heading vector stays a unit vector over the 4 N steps of every candidate
+    assert np.abs(np.sqrt((d["heading_end"] ** 2).sum(-1)) - 1.0).max() <= 1e-12
+    # the two classes really pass on opposite sides of the obstacle at y = 0.05
+    ys = [out["guidance"][s, p, np.argmin(np.abs(out["guidance"][s, p, :, 0] - 6.0)), 1] for p in range(2)]
+    left_bit = [int(out["sig_side"][s, p]) & 1 for p in range(2)]
+    for y, b in zip(ys, left_bit):
+        assert (y < 0.05) == (b == 1)          # obstacle on the left <=> the trajectory passes below it
+
+
+@pytest.mark.parametrize("name", ["none", "out_of_range", "past_the_end"])
+def test_equal_candidates_are_one_class(first, name):
+    s, out = scene_of(name), first["out"]
+    K = 2 * (G - 1)
+    assert out["n_found"][s] == 1
+    assert out["topology"][s].tolist() == [0] + [-1] * (G - 2) + [K]
+    assert out["enabled"][s].tolist() == [1] + [0] * (G - 2) + [1]
+    assert not out["details"][s]["relevant"].any()
+    # disabled planners' guidance rows are left as they were
+    assert (out["guidance"][s, 1:] == -7.0).all() and np.isfinite(out["guidance"][s, 0]).all()
+    np.testing.assert_array_equal(out["guidance"][s, 0, 0, 0:2], first["state"][s, 0:2])
+
+
+def test_past_the_end_of_the_window_the_nominal_stalls(first):
+    s = scene_of("past_the_end")
+    g = first["out"]["guidance"][s, 0]
+    # the nominal is the end point (10, 0) for ever: the unicycle turns round towards it within its bounds
+    assert np.isfinite(g).all() and g[-1, 0] < g[:, 0].max()
+
+
+def test_more_than_three_relevant_obstacles(first):
+    s, d = scene_of("five"), first["out"]["details"][scene_of("five")]
+    assert d["relevant"][:5].all() and not d["relevant"][5:].any()
+    assert d["rank"][:5].tolist() == [2, 0, 4, 1, 3]            # by time of closest approach
+    assert (np.diff(d["closest_index"][[1, 3, 0, 4, 2]]) > 0).all()
+    for c in range(8):
+        for j in range(5):
+            left = (d["requested"][c] >> j) & 1
+            if d["rank"][j] < 3:
+                assert left == (c >> d["rank"][j]) & 1
+            else:
+                assert left == int(d["lateral"][j] >= 0.0)      # slot 4 lies right, slot 2 left: they keep their side
+    assert d["lateral"][4] < 0.0 < d["lateral"][2]
+
+
+def test_an_infeasible_candidate_is_dropped(first):
+    s, out = scene_of("walled"), first["out"]
+    d = out["details"][s]
+    bad = [c for c in range(8) if not d["clearance"][c] >= ns.GUIDANCE_CLEARANCE]
+    assert bad and not set(bad) & set(d["order"])
+    assert 1 <= out["n_found"][s] < 8 - len(bad) + 1
+    for p in range(int(out["n_found"][s])):
+        assert d["clearance"][d["order"][p]] >= ns.GUIDANCE_CLEARANCE
+    # a scene in which nothing is feasible: every guided planner disabled, the non-guided one enabled
+    box = [((1.2, 0.0), (0.0, 0.0), 0.4), ((1.0, 0.9), (0.0, 0.0), 0.4), ((1.0, -0.9), (0.0, 0.0), 0.4),
+           ((0.3, 1.2), (0.0, 0.0), 0.4), ((0.3, -1.2), (0.0, 0.0), 0.4)]
+    state, sp, ob, me = gc.stack([gc.scene(LAY, box, v=1.5)])
+    o = gd.guidance_update_host(LAY, state, sp, ob, me, gd.initial_state(1, G, LAY.N), np.zeros((1, G, LAY.N + 1, 4)),
+                                G, gc.SETTINGS)
+    assert o["n_found"][0] == 0 and o["enabled"][0].tolist() == [0] * (G - 1) + [1]
+    assert (o["topology"][0, :G - 1] == -1).all() and (o["guidance"] == 0.0).all()
+
+
+def test_class_ids_persist_and_are_recycled(first):
+    K = 2 * (G - 1)
+    o1 = first["out"]
+    S = len(first["state"])
+    st = dict(first["st"], class_traj=o1["class_traj"], class_used=o1["class_used"])
+    guided = np.ones((S, G), np.uint8)
+    guided[:, G - 1] = 0
+    st.update(gd.select_host(np.array([0, 1, G - 1, 0, -1, 0]), guided, o1["topology"], o1["enabled"]))
+    # the second update: the ego moved on, the obstacle rows reversed
+    state, sp, ob, me = gc.update_case(LAY, 1)
+    o2 = gd.guidance_update_host(LAY, state, sp, ob, me, st, o1["guidance"], G, gc.SETTINGS, details=True)
+    np.testing.assert_array_equal(o2["n_found"], o1["n_found"])
+    np.testing.assert_array_equal(o2["topology"], o1["topology"])
+    assert o2["topology"].max() == K and o2["topology"][:, :G - 1].max() < K
+    s = scene_of("ahead")
+    for p in range(2):        # the same id means the same side of the (moved) obstacle slot
+        assert (int(o1["sig_side"][s, p]) & 1) == (int(o2["sig_side"][s, p]) >> 7) & 1
+    # every planner that kept its class has existing guidance (mapGuidanceTrajectoriesToPlanners)
+    np.testing.assert_array_equal(o2["existing_guidance"], (o2["enabled"] > 0) & (guided > 0))
+    # the class-keyed flags: scene 1 selected class topology[1, 1], scene 2 the non-guided planner,
+    # scene 4 failed
+    assert o2["previously_selected"][1].tolist() == [0, 1] + [0] * (G - 2)
+    assert o2["consistency_on"][1].tolist() == [0, 1] + [0] * (G - 2)
+    assert o2["consistency_on"][2].tolist() == [0] * (G - 1) + [1] and not o2["previously_selected"][2].any()
+    assert not o2["consistency_on"][4].any() and not o2["previously_selected"][4].any()
+    # a class that disappears frees its id: the obstacle of "ahead" moves out of range, one class is left
+    st2 = dict(st, class_traj=o2["class_traj"], class_used=o2["class_used"])
+    ob3 = ob.copy()
+    ob3[s, 7, :, 1] += 4.0
+    o3 = gd.guidance_update_host(LAY, state, sp, ob3, me, st2, o2["guidance"], G, gc.SETTINGS)
+    assert o3["n_found"][s] == 1 and o3["topology"][s, 0] == 0
+    assert o3["class_used"][s].tolist() == [1] + [0] * (K - 1)
+    # a new class takes the lowest free id: only id 1 in use (the class that passes with the obstacle on the
+    # side of the second trajectory of the second update), ids 0 and 2.. free
+    st3 = dict(st2, class_traj=o2["class_traj"].copy(), class_used=o2["class_used"].copy())
+    st3["class_used"][s] = 0
+    st3["class_used"][s, 1] = 1
+    o4 = gd.guidance_update_host(LAY, state, sp, ob, me, st3, o2["guidance"], G, gc.SETTINGS)
+    assert o4["n_found"][s] == 2
+    ids = o4["topology"][s, :2].tolist()
+    assert sorted(ids) == [0, 1]
+    kept = ids.index(1)
+    assert int(o4["sig_side"][s, kept]) == int(o2["sig_side"][s, 1])       # id 1 stayed with its class
+    assert o4["class_used"][s].tolist() == [1, 1] + [0] * (K - 2)
+
+
+@pytest.mark.parametrize("planner_class,found,existing,taken,mapping", [
+    # the first step: nobody has a class, the first remaining trajectory takes EVERY planner (no `break`)
+    ([-1, -1, -1, -1], [0, 1], [0, 0, 0, 0], [1, 1, 1, 1], {0: 3}),
+    # every class kept
+    ([0, 1, -1, 6], [0, 1], [1, 1, 0, 0], [1, 1, 0, 0], {0: 0, 1: 1}),
+    # classes swapped between planners: existing guidance all the same
+    ([1, 0, -1, 6], [0, 1], [1, 1, 0, 0], [1, 1, 0, 0], {0: 1, 1: 0}),
+    # one remaining trajectory, two untaken planners (and the non-guided one): all marked taken, the
+    # trajectory mapped to the last of them
+    ([0, -1, -1, 6], [0, 2], [1, 0, 0, 0], [1, 1, 1, 1], {0: 0, 1: 3}),
+    # two remaining trajectories: the second finds nothing left and is mapped nowhere
+    ([5, -1, -1, 6], [0, 2], [0, 0, 0, 0], [1, 1, 1, 1], {0: 3}),
+    # two trajectories of one class: the second takes the next planner of that class, or remains
+    ([3, 3, -1, 6], [3, 3, 3], [1, 1, 0, 0], [1, 1, 1, 1], {0: 0, 1: 1, 2: 3}),
+    # nothing found
+    ([0, 1, -1, 6], [], [0, 0, 0, 0], [0, 0, 0, 0], {}),
+])
+def test_map_planners_host(planner_class, found, existing, taken, mapping):
+    m = gd.map_planners_host(np.array(planner_class), found)
+    assert m["existing_guidance"].astype(int).tolist() == existing
+    assert m["taken"].astype(int).tolist() == taken
+    assert m["mapping"] == mapping
+
+
+@pytest.mark.parametrize("cong", [True, False])
+@pytest.mark.parametrize("present", [True, False])
+@pytest.mark.parametrize("selected", ["guided", "non_guided", "failed"])
+def test_flags(selected, present, cong):
+    """(selected guided class / non-guided / all failed) x (class still present / gone) x
+    consistency_on_non_guided, against shouldEnableConsistencyForPlanner and :418 written out."""
+    Gs, K = 4, 6
+    guided = np.array([1, 1, 1, 0])
+    topology = np.array([2, 4 if present else 5, -1, K])
+    enabled = np.array([1, 1, 0, 1])
+    sel, orig = {"guided": (4, False), "non_guided": (K, True), "failed": (-1, False)}[selected]
+    ps, on = gd.planner_flags_host(topology, enabled, guided, sel, orig, cong)
+    want_ps, want_on = [0] * Gs, [0] * Gs
+    if selected == "guided" and present:
+        want_ps[1] = want_on[1] = 1
+    if selected == "non_guided" and cong:
+        want_on[3] = 1
+    assert ps.astype(int).tolist() == want_ps and on.astype(int).tolist() == want_on
+    # a disabled planner (topology -1) is never flagged, even after a failed step (selected -1)
+    assert not ps[2] and not on[2]
+
+
+def test_select_host():
+    guided = np.array([[1, 1, 0]] * 3)
+    topology = np.array([[3, -1, 4], [0, 1, 4], [2, 3, 4]], np.int32)
+    enabled = np.array([[1, 0, 1], [1, 1, 1], [1, 1, 1]])
+    r = gd.select_host(np.array([2, -1, 1]), guided, topology, enabled)
+    assert r["selected_topology"].tolist() == [4, -1, 3] and r["prev_was_original"].tolist() == [1, 0, 0]
+    assert r["planner_class"].tolist() == [[3, -1, 4], [0, 1, 4], [2, 3, 4]]
+    ex = gd.mask_host(np.array([1, 1, 0, 1, 2, 1, 1, 1, 1]), enabled)
+    assert ex.tolist() == [1, ns.GUIDANCE_EXIT_DISABLED, 0, 1, 2, 1, 1, 1, 1]
+    assert ns.GUIDANCE_EXIT_DISABLED not in (0, 1, 2, 3, 4)
+
+
+def test_shape_limits_of_the_host_restatement():
+    state, sp, ob, me = gc.update_case(LAY, 0)
+    with pytest.raises(ValueError):
+        gd.guidance_update_host(LAY, state, sp, ob, me, gd.initial_state(6, 10, LAY.N), np.zeros((6, 10, 21, 4)), 10,
+                                gc.SETTINGS)
+
+
+def test_a_loop_without_a_layer_is_what_it_was():
+    """The hooks are additive: no layer by default, and the host loop functions keep deriving the flags
+    by planner index (producers.advance_host), as the existing closed-loop tests rely on."""
+    from oscar_mpc_planner_mr_modification_amd import producers
+    from oscar_mpc_planner_mr_modification_amd.control_loop import ControlLoop
+    from oscar_mpc_planner_mr_modification_amd.fleet import FleetLoop
+    assert inspect.signature(ControlLoop.__init__).parameters["guidance_layer"].default is None
+    assert inspect.signature(FleetLoop.step).parameters["topology"].default is None
+    lay = config_layout("C1")
+    S, Gs, N = 2, 3, lay.N
+    rng = np.random.default_rng(0)
+    xt, ut = rng.normal(size=(S * Gs, N + 1, 5)), rng.normal(size=(S * Gs, N, 2))
+    warm = rng.normal(size=(S * Gs, N + 1, 7))
+    guided = np.array([[1, 1, 0]] * S, bool)
+    c = producers.advance_host(lay, np.array([1, 2]), np.ones(S * Gs, np.int32), xt, ut, warm, None,
+                               rng.normal(size=(S, 5)), guided, lay.dt)
+    assert c.consistency_on.astype(int).tolist() == [[0, 1, 0], [0, 0, 1]]
+    assert c.previously_selected.astype(int).tolist() == [[0, 1, 0], [0, 0, 0]]
+
+
+def test_cpu_guidance_loop_changes_its_classes(oracle_mod):
+    """The closed loop of tests/test_gpu_guidance.py on the CPU alone: three steps of gc.LOOP_CASE."""
+    import copy
+
+    import producers_oracle
+    lay, sc = gc.loop_scenes()
+    loop = gc.GuidanceCpuLoop(lay, copy.deepcopy(sc), oracle_mod, producers_oracle)
+    hist = []
+    for _ in range(3):
+        h = loop.step()
+        hist.append(h)
+        # a disabled planner never wins, and every exit code of one is the disabled code
+        dis = h["enabled"].reshape(-1) == 0
+        assert (h["exit"][dis] == ns.GUIDANCE_EXIT_DISABLED).all() and (h["exit"][~dis] != ns.GUIDANCE_EXIT_DISABLED).all()
+        for s, b in enumerate(h["best"]):
+            assert b < 0 or h["enabled"][s, b]
+        loop.advance(h["best"])
+    changed = gc.assert_loop_is_decisive(loop.details, hist)
+    print("scenes whose classes change:", changed, [h["n_found"].tolist() for h in hist])
+
+
+def test_cpu_fleet_guidance_loop_is_decisive(oracle_mod):
+    """The fleet's closed loop of tests/test_gpu_guidance.py on the CPU alone (gc.FLEET_CASE): robot
+    obstacles appear from the second step, a non-guided winner is published with reason 6, and the
+    class ids reach publish_host."""
+    import copy
+
+    import producers_oracle
+    case = gc.fleet_case()
+    loop = gc.fleet_cpu_loop(case, copy.deepcopy(case["scenes"]), oracle_mod, producers_oracle)
+    hist = []
+    for step in range(3):
+        h = loop.step(0.05 * step)
+        hist.append(h)
+        loop.advance(h["best"])
+    gc.assert_loop_is_decisive(loop.details, hist)
+    G = case["G"]
+    assert any((h["best"] == G - 1).any() for h in hist) and any((h["reason"] == 6).any() for h in hist)
+    assert (hist[0]["published"] == 1).all() and not (hist[2]["published"] == 1).all()
+    print([h["n_found"].tolist() for h in hist], [h["reason"].tolist() for h in hist])
+
+
+# ------------------------------------------------------------------ C ABI
+
+
+def declared_functions():
+    txt = open(HDR).read()
+    return sorted(set(re.findall(r"^\s*(?:int|const char \*|void)\s*\**\s*(mpcg_\w+)\s*\(", txt, re.M)))
+
+
+def test_library_exports_every_function_of_the_guidance_header():
+    if not os.path.exists(LIB):
+        from oscar_mpc_planner_mr_modification_amd import _build
+        _build.build_lib()
+    names = declared_functions()
+    assert names == ["mpcg_guidance_mask", "mpcg_guidance_select", "mpcg_guidance_update"]
+    out = subprocess.run(["nm", "-D", "--defined-only", LIB], capture_output=True, text=True, check=True).stdout
+    exported = set(l.split()[-1] for l in out.splitlines() if l.strip())
+    for n in names:
+        assert n in exported, n
+
+
+def test_python_binding_mirrors_the_header():
+    assert set(ns.GUIDANCE_EXPORTS) == set(declared_functions())
+    raw = open(HDR).read()
+    txt = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
+    for struct, mirror in (("mpcg_guidance_settings", ns.MpcgGuidanceSettings),
+                           ("mpcg_guidance_state", ns.MpcgGuidanceState), ("mpcg_guidance_out", ns.MpcgGuidanceOut)):
+        body = txt[txt.index(f"typedef struct {struct} {{"):txt.index(f"}} {struct};")]
+        names = []
+        for decl in re.findall(r"(?:unsigned\s+)?(?:int|double|char)\s+([^;]+);", body):
+            names += [p.replace("*", "").strip() for p in decl.split(",")]
+        assert names == [f[0] for f in mirror._fields_], struct
+    macros = dict(re.findall(r"#define MPCG_GUIDANCE_(\w+) \(?([-\de.]+)\)?", raw))
+    for name, value in macros.items():
+        assert float(value) == float(getattr(ns, "GUIDANCE_" + name)), name
+    assert len(macros) == 16
+
+
+def test_guidance_sources_are_linked_outside_the_source_hash():
+    from oscar_mpc_planner_mr_modification_amd import _build
+    assert _build.GUIDANCE_SOURCES == {"mpcg_guidance.hip": ["-ffp-contract=off"]}
+    assert _build.GUIDANCE_HEADERS == ["mpcg_guidance.h"]
+    assert "mpcg_guidance.hip" not in _build.SOURCES and "mpcg_guidance.h" not in _build.HEADERS
+
+
+def test_bad_arguments_are_reported_without_a_launch():
+    """Every -1 / -2 of the three entry points (host-side checks only; the pointers are never read on
+    the device)."""
+    lib = C.CDLL(LIB)
+    lib.mpcg_last_error.restype = C.c_char_p
+    vp = C.c_void_p
+    lib.mpcg_guidance_update.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.mpcg_guidance_mask.argtypes = [C.c_int, C.c_int, vp, vp, vp]
+    lib.mpcg_guidance_select.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]
+    pr = ns.problem_from_layout(LAY)
+    S = 3
+
+    def check(rc, want, word):
+        assert rc == want and word in lib.mpcg_last_error().decode(), (rc, lib.mpcg_last_error())
+
+    def update(pr_=pr, Gs=G, st=None, out=None, set_=None, state=1, sp=1, ob=1, me=1, null=()):
+        st = ns.MpcgGuidanceState(1, 1, 1, 1, 1) if st is None else st
+        out = ns.MpcgGuidanceOut(*([1] * 12)) if out is None else out
+        set_ = ns.MpcgGuidanceSettings(0.325, 2.0, 1) if set_ is None else set_
+        ref = lambda name, v: None if name in null else C.byref(v)  # noqa: E731
+        return lib.mpcg_guidance_update(ref("pr", pr_), S, Gs, ref("set", set_), state, sp, ob, me, ref("st", st),
+                                        ref("out", out), None)
+
+    for name in ("pr", "set"):
+        check(update(null=(name,)), -1, "invalid arguments")
+    for kw in ("state", "sp"):
+        check(update(**{kw: None}), -1, "invalid arguments")
+    for kw in ("ob", "me"):
+        check(update(**{kw: None}), -1, "null obstacle rows")
+    check(update(null=("st",)), -1, "null layer state")
+    for f, _ in ns.MpcgGuidanceState._fields_:
+        st = ns.MpcgGuidanceState(1, 1, 1, 1, 1)
+        setattr(st, f, None)
+        check(update(st=st), -1, "null layer state")
+    check(update(null=("out",)), -1, "null output")
+    for f, _ in ns.MpcgGuidanceOut._fields_:
+        out = ns.MpcgGuidanceOut(*([1] * 12))
+        setattr(out, f, None)
+        check(update(out=out), -1, "null output")
+    check(update(set_=ns.MpcgGuidanceSettings(-0.1, 2.0, 1)), -1, "robot_radius")
+    check(lib.mpcg_guidance_update(C.byref(pr), -1, G, C.byref(ns.MpcgGuidanceSettings(0.3, 2.0, 1)), 1, 1, 1, 1,
+                                   C.byref(ns.MpcgGuidanceState(1, 1, 1, 1, 1)),
+                                   C.byref(ns.MpcgGuidanceOut(*([1] * 12))), None), -1, "invalid arguments")
+
+    def changed(**kw):
+        p = ns.problem_from_layout(LAY)
+        for k, v in kw.items():
+            setattr(p, k, v)
+        return p
+
+    check(update(pr_=changed(dt=0.0)), -1, "dt > 0")
+    check(update(pr_=changed(i_spline0=LAY.npar - 9 * LAY.n_seg + 1)), -1, "outside the stage parameters")
+    check(update(pr_=changed(nx=6)), -2, "nx 5")
+    check(update(pr_=changed(N=1)), -2, "N <= 32")
+    check(update(pr_=changed(N=33)), -2, "N <= 32")
+    check(update(pr_=changed(n_ell=33)), -2, "n_ell <= 32")
+    check(update(pr_=changed(n_seg=9)), -2, "n_seg <= 8")
+    check(update(pr_=changed(n_seg=0)), -2, "n_seg <= 8")
+    check(update(Gs=1), -2, "guided planners")
+    check(update(Gs=10), -2, "guided planners")
+
+    check(lib.mpcg_guidance_mask(S, G, None, 1, None), -1, "invalid arguments")
+    check(lib.mpcg_guidance_mask(S, G, 1, None, None), -1, "invalid arguments")
+    check(lib.mpcg_guidance_mask(-1, G, 1, 1, None), -1, "invalid arguments")
+    check(lib.mpcg_guidance_mask(S, 0, 1, 1, None), -1, "invalid arguments")
+    check(lib.mpcg_guidance_mask(S, 10, 1, 1, None), -2, "guided planners")
+
+    def select(Gs=G, best=1, guided=1, topo=1, en=1, st=1):
+        st_ = ns.MpcgGuidanceState(1, 1, 1, 1, 1)
+        return lib.mpcg_guidance_select(S, Gs, best, guided, topo, en, None if st is None else C.byref(st_), None)
+
+    for kw in ("best", "guided", "topo", "en"):
+        check(select(**{kw: None}), -1, "invalid arguments")
+    check(select(Gs=0), -1, "invalid arguments")
+    check(select(st=None), -1, "null layer state")
+    check(select(Gs=10), -2, "guided planners")
+    # no launch for an empty batch
+    assert lib.mpcg_guidance_update(C.byref(pr), 0, G, C.byref(ns.MpcgGuidanceSettings(0.3, 2.0, 1)), 1, 1, 1, 1,
+                                    C.byref(ns.MpcgGuidanceState(1, 1, 1, 1, 1)),
+                                    C.byref(ns.MpcgGuidanceOut(*([1] * 12))), None) == 0
+    assert lib.mpcg_guidance_mask(0, G, 1, 1, None) == 0
+    assert lib.mpcg_guidance_select(0, G, 1, 1, 1, 1, C.byref(ns.MpcgGuidanceState(1, 1, 1, 1, 1)), None) == 0
