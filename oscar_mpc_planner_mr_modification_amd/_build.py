@@ -30,6 +30,9 @@ PATH_HEADERS = ["mpcg_path.h"]
 # the guidance layer (include/mpcg_guidance.h): linked in the same way, outside source_hash()
 GUIDANCE_SOURCES = {"mpcg_guidance.hip": ["-ffp-contract=off"]}
 GUIDANCE_HEADERS = ["mpcg_guidance.h"]
+# the active-solve compaction (include/mpcg_active.h): linked in the same way, outside source_hash()
+ACTIVE_SOURCES = {"mpcg_active.hip": ["-ffp-contract=off"]}
+ACTIVE_HEADERS = ["mpcg_active.h"]
 HOST_SOURCES = ["host/mpcg_yaml.cpp", "host/mpcg_solver.cpp"]
 HOST_HEADERS = ["mpc_planner_solver/mpcg_yaml.h", "mpc_planner_solver/mpcg_config.h", "mpc_planner_solver/state.h",
                 "mpc_planner_solver/mpcg_solver_interface.h", "mpc_planner_solver/solver_interface.h"]
@@ -63,10 +66,12 @@ def build_lib(force: bool = False, verbose: bool = False, extra_flags=(), out: s
     """libmpcg.so (or a diagnostic / variant build of it with extra_flags at `out`; `sources`
     restricts the built-in instance files of such a build)"""
     srcs = SOURCES if sources is None else {k: v for k, v in SOURCES.items() if k in sources}
-    srcs = {**srcs, **FLEET_SOURCES, **PATH_SOURCES, **GUIDANCE_SOURCES}
+    srcs = {**srcs, **FLEET_SOURCES, **PATH_SOURCES, **GUIDANCE_SOURCES, **ACTIVE_SOURCES}
     deps = [os.path.join(CSRC, s) for s in list(SOURCES) + HEADERS + list(FLEET_SOURCES) + FLEET_HEADERS +
-            list(PATH_SOURCES) + PATH_HEADERS + list(GUIDANCE_SOURCES) + GUIDANCE_HEADERS] + \
-        [os.path.join(INCLUDE, h) for h in ("mpcg.h", "mpcg_fleet.h", "mpcg_path.h", "mpcg_guidance.h")] + [__file__]
+            list(PATH_SOURCES) + PATH_HEADERS + list(GUIDANCE_SOURCES) + GUIDANCE_HEADERS +
+            list(ACTIVE_SOURCES) + ACTIVE_HEADERS] + \
+        [os.path.join(INCLUDE, h) for h in ("mpcg.h", "mpcg_fleet.h", "mpcg_path.h", "mpcg_guidance.h",
+                                            "mpcg_active.h")] + [__file__]
     if not force and not _stale(out, deps):
         return out
     objdir = os.path.join(BUILD, "obj" + ("_" + "_".join(f.strip("-").replace("=", "") for f in extra_flags)

@@ -3,7 +3,8 @@ GuidanceConstraints::optimize and Planner::solveMPC do per step, with every
 per-step quantity device-resident.
 
     step():  mpcg_prepare (per-guess inputs) -> mpcg_solve (all guesses, carried
-             multipliers) -> mpcg_select_best_device (FindBestPlanner with the
+             multipliers; with skip_disabled mpcg_solve_active: the enabled guesses only)
+             -> mpcg_select_best_device (FindBestPlanner with the
              consistency / selection-weight bookkeeping) -> mpcg_advance (warm
              start, previous plan, selection flags, multipliers of the next step)
 
@@ -21,9 +22,11 @@ class ControlLoop:
     def __init__(self, layout: Layout, scenes, device, robot_radius: float, w_consistency: float,
                  selection_weight: float, deceleration: float = 3.0, shift_forward: bool = False,
                  consistency_on_non_guided: bool = True, elapsed: float | None = None,
-                 warmstart_with_mpc_solution: bool = False, guidance_layer=None):
+                 warmstart_with_mpc_solution: bool = False, guidance_layer=None, skip_disabled: bool = False):
         import torch
 
+        if skip_disabled and guidance_layer is None:
+            raise ValueError("ControlLoop: skip_disabled needs a guidance_layer (the layer is what disables planners)")
         self.lay = layout
         self.pr = native.problem_from_layout(layout)
         self.dev = device
@@ -42,6 +45,11 @@ class ControlLoop:
         # guidance.GuidanceLayer or None: with a layer, guidance, existing_guidance and the class-keyed
         # selection flags of every step come from mpcg_guidance_update instead of from outside
         self.guidance_layer = guidance_layer
+        # skip_disabled: the planners the layer disables are not solved (mpcg_solve_active)
+        # instead of solved and masked afterwards; their outputs then hold the fill of include/mpcg_active.h.
+        # One host synchronisation per step (the count of enabled planners); step() adds n_active.
+        self.skip_disabled = bool(skip_disabled)
+        self.active_ws = native.ActiveWorkspace(self.pr, self.S * self.G, with_lam=True) if self.skip_disabled else None
 
     def set_scene_data(self, state, obst, guidance, existing_guidance=None):
         """Replace the externally provided scene data (device tensors or arrays).
@@ -63,7 +71,8 @@ class ControlLoop:
             self.existing = ex.to(torch.uint8).contiguous()
 
     def step(self, stream=None):
-        """One control step of every scene.  Returns dict(best, exit, xtraj, utraj, pobj, objective, prepared)."""
+        """One control step of every scene.  Returns dict(best, exit, xtraj, utraj, pobj, objective, prepared)
+        (plus n_active, the number of planners solved, with skip_disabled)."""
         pr, S, G, N = self.pr, self.S, self.G, self.lay.N
         gl = self.guidance_layer
         if gl is not None:
@@ -75,10 +84,14 @@ class ControlLoop:
                 self.dsc["existing_guidance"] = gl.existing_guidance
         prep = native.prepare_device(pr, self.dsc, self.rr, self.wc, self.dec, stream=stream,
                                      warmstart_with_mpc_solution=self.own_warm, shift_forward=self.shift)
-        out = native.solve_batch_device(pr, prep["params"], prep["warm"], prep["xinit"], stream=stream,
-                                        lam_in=self.lam, lam_out=True)
-        if gl is not None:
-            gl.mask(out["exit"], stream=stream)
+        if self.skip_disabled:
+            out = native.solve_active_device(pr, prep["params"], prep["warm"], prep["xinit"], gl.enabled.reshape(-1),
+                                             ws=self.active_ws, stream=stream, lam_in=self.lam, lam_out=True)
+        else:
+            out = native.solve_batch_device(pr, prep["params"], prep["warm"], prep["xinit"], stream=stream,
+                                            lam_in=self.lam, lam_out=True)
+            if gl is not None:
+                gl.mask(out["exit"], stream=stream)
         best, objective = native.select_best_device(S, G, N, out["xtraj"], out["pobj"], out["exit"],
                                                     prev_traj=prep["prev_interp"], w_cons=self.wc,
                                                     consistency_enabled=prep["consistency_active"],
@@ -86,6 +99,8 @@ class ControlLoop:
                                                     selection_weight=self.sw, stream=stream)
         self.last = dict(best=best, exit=out["exit"], xtraj=out["xtraj"], utraj=out["utraj"], pobj=out["pobj"],
                          objective=objective, prepared=prep, lam=out["lam"])
+        if self.skip_disabled:
+            self.last["n_active"] = out["n_active"]
         if gl is not None:
             gl.after_select(self, self.last, stream=stream)
         return self.last

@@ -233,7 +233,8 @@ class FleetLoop:
                     robot, straight into the loop's obst / obst_meta) -> ControlLoop.step ->
                     mpcg_fleet_publish (plan, topology, trigger, the per-sender state)
 
-    Guidance trajectories still come from outside (`loop.set_scene_data`)."""
+    Guidance trajectories still come from outside (`loop.set_scene_data`).  loop_options are ControlLoop's
+    keywords (guidance_layer=..., skip_disabled=True: the planners the layer disables are not solved)."""
 
     def __init__(self, layout, scenes, F: int, R: int, device, settings: FleetSettings, robot_radius: float,
                  w_consistency: float, selection_weight: float, **loop_options):

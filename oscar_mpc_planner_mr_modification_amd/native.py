@@ -10,7 +10,8 @@ import os
 
 import numpy as np
 
-from .native_spec import (ABI_VERSION, DEFAULT_OPTIONS, EXPORTS, FLEET_EXPORTS, GUIDANCE_CANDIDATES,  # noqa: F401
+from .native_spec import (ABI_VERSION, ACTIVE_EXPORTS, DEFAULT_OPTIONS, EXPORTS, FLEET_EXPORTS,  # noqa: F401
+                          GUIDANCE_CANDIDATES,
                           GUIDANCE_EXPORTS, INFO_STRIDE, NU, NVAR, NX, PATH_EXPORTS, STATS_STRIDE, UNICYCLE_LB,
                           UNICYCLE_UB, MpcgFleetSettings, MpcgFleetState, MpcgGuidanceOut, MpcgGuidanceSettings,
                           MpcgGuidanceState, MpcgIo, MpcgPathSettings, MpcgPathTable, MpcgProblem, MpcgSceneIo,
@@ -91,6 +92,22 @@ def _load():
     lib.mpcg_guidance_mask.restype = C.c_int
     lib.mpcg_guidance_select.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, C.POINTER(MpcgGuidanceState), vp]
     lib.mpcg_guidance_select.restype = C.c_int
+    # include/mpcg_active.h
+    IO = C.POINTER(MpcgIo)
+    lib.mpcg_active_plan.argtypes = [C.c_int, vp, vp, vp, vp, vp]
+    lib.mpcg_active_plan.restype = C.c_int
+    lib.mpcg_active_gather.argtypes = [P, C.c_int, vp, IO, IO, vp]
+    lib.mpcg_active_gather.restype = C.c_int
+    lib.mpcg_active_scatter.argtypes = [P, C.c_int, vp, IO, IO, vp]
+    lib.mpcg_active_scatter.restype = C.c_int
+    lib.mpcg_active_ws_create.argtypes = [P, C.c_int, C.c_int, C.c_int, C.c_int]
+    lib.mpcg_active_ws_create.restype = vp
+    lib.mpcg_active_ws_destroy.argtypes = [vp]
+    lib.mpcg_active_ws_destroy.restype = None
+    lib.mpcg_active_ws_read_plan.argtypes = [vp, C.c_int, vp, vp, vp]
+    lib.mpcg_active_ws_read_plan.restype = C.c_int
+    lib.mpcg_solve_active.argtypes = [P, C.c_int, IO, vp, vp, C.POINTER(C.c_int), vp]
+    lib.mpcg_solve_active.restype = C.c_int
     # (MPCG_ABI_ACCEPT_OLDER, A/B timing runs of an earlier round's library only: ABI versions whose
     # mpcg_problem is a prefix of this one -- later ABIs only append fields)
     older = {int(v) for v in os.environ.get("MPCG_ABI_ACCEPT_OLDER", "").split(",") if v.strip().isdigit()}
@@ -631,3 +648,171 @@ def guidance_select_device(S: int, G: int, best, guided, topology, enabled, gsta
     s = stream if stream is not None else torch.cuda.current_stream(best.device)
     _check(lib.mpcg_guidance_select(S, G, _ptr(best), _ptr(guided), _ptr(topology), _ptr(enabled), C.byref(st),
                                     C.c_void_p(s.cuda_stream)), "mpcg_guidance_select")
+
+
+def active_plan_device(enabled, slot_of=None, solve_of=None, n_active=None, stream=None):
+    """mpcg_active_plan (include/mpcg_active.h): the stable compaction of enabled (B,) uint8 (any shape
+    of B elements).  Returns slot_of (B,), solve_of (B,) and n_active (1,), int32 device tensors
+    (allocated unless given); asynchronous on `stream`."""
+    import torch
+
+    assert enabled.dtype == torch.uint8 and enabled.is_cuda and enabled.is_contiguous()
+    B, dev = enabled.numel(), enabled.device
+    slot_of = torch.empty((B,), dtype=torch.int32, device=dev) if slot_of is None else slot_of
+    solve_of = torch.empty((B,), dtype=torch.int32, device=dev) if solve_of is None else solve_of
+    n_active = torch.empty((1,), dtype=torch.int32, device=dev) if n_active is None else n_active
+    for t_, n in ((slot_of, B), (solve_of, B), (n_active, 1)):
+        assert t_.dtype == torch.int32 and t_.is_cuda and t_.is_contiguous() and t_.numel() == n
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    # (an empty tensor's data_ptr is 0: the plan of an empty batch still needs non-null pointers)
+    p = lambda t_: C.c_void_p(t_.data_ptr() or n_active.data_ptr())  # noqa: E731
+    _check(lib.mpcg_active_plan(B, p(enabled), p(slot_of), p(solve_of), _ptr(n_active), C.c_void_p(s.cuda_stream)),
+           "mpcg_active_plan")
+    return slot_of, solve_of, n_active
+
+
+_IO_KEYS = (("params", "params"), ("warm", "warm"), ("xinit", "xinit"), ("lam_in", "lam_in"), ("xtraj", "xtraj"),
+            ("utraj", "utraj"), ("pobj", "pobj"), ("exit_code", "exit"), ("info", "info"), ("lam_out", "lam"),
+            ("qp_in", "qp_in"), ("qp_out", "qp"), ("stats", "stats"))
+
+
+def _active_io(pr: MpcgProblem, d: dict, rows: int) -> MpcgIo:
+    """An mpcg_io over the tensors of `d` (keys of solve_batch_device's arguments and result: params, warm,
+    xinit, lam_in, qp_in, xtraj, utraj, pobj, exit, info, lam, qp, stats; missing or None: NULL), each
+    checked to hold at least `rows` blocks of the size include/mpcg.h documents."""
+    import torch
+
+    N, nx, nu = pr.N, pr.nx, pr.nu
+    LS = lam_stride(pr)
+    Q = qp_mem_size(pr) if (d.get("qp_in") is not None or d.get("qp") is not None) else 0
+    block = dict(params=N * pr.npar, warm=(N + 1) * (nu + nx), xinit=nx, lam_in=N * LS, xtraj=(N + 1) * nx,
+                 utraj=N * nu, pobj=1, exit=1, info=INFO_STRIDE, lam=N * LS, qp_in=Q, qp=Q, stats=STATS_STRIDE)
+    ptrs = []
+    for _, k in _IO_KEYS:
+        t_ = d.get(k)
+        if t_ is not None:
+            want = torch.int32 if k in ("exit", "info") else torch.float64
+            assert t_.dtype == want and t_.is_cuda and t_.is_contiguous(), k
+            assert t_.numel() >= rows * block[k] and (t_.shape[0] == 0 or t_.numel() == t_.shape[0] * block[k]), \
+                (k, tuple(t_.shape), rows, block[k])
+        ptrs.append(None if t_ is None else t_.data_ptr())
+    return MpcgIo(*ptrs)
+
+
+def active_gather_device(pr: MpcgProblem, slot_of, full: dict, dense: dict, stream=None):
+    """mpcg_active_gather: params, warm, xinit (and lam_in / qp_in where present in both) of every enabled
+    solve b of `full` (B rows) into row slot_of[b] of `dense` (at least as many rows as are enabled; the
+    caller's responsibility, B rows always suffice).  Dicts of device tensors, keys as in _active_io."""
+    import torch
+
+    B = slot_of.numel()
+    assert slot_of.dtype == torch.int32 and slot_of.is_cuda and slot_of.is_contiguous()
+    assert full["params"].shape[0] == B
+    fio, dio = _active_io(pr, full, B), _active_io(pr, dense, 0)
+    s = stream if stream is not None else torch.cuda.current_stream(slot_of.device)
+    _check(lib.mpcg_active_gather(C.byref(pr), B, _ptr(slot_of), C.byref(fio), C.byref(dio),
+                                  C.c_void_p(s.cuda_stream)), "mpcg_active_gather")
+
+
+def active_scatter_device(pr: MpcgProblem, slot_of, dense: dict, full: dict, stream=None):
+    """mpcg_active_scatter: every output present in `full` (xtraj, utraj, pobj, exit, info, lam, qp, stats; B
+    rows) from row slot_of[b] of `dense`; a disabled solve gets the fill of include/mpcg_active.h, which
+    reads full["warm"]."""
+    import torch
+
+    B = slot_of.numel()
+    assert slot_of.dtype == torch.int32 and slot_of.is_cuda and slot_of.is_contiguous()
+    fio, dio = _active_io(pr, full, B), _active_io(pr, dense, 0)
+    s = stream if stream is not None else torch.cuda.current_stream(slot_of.device)
+    _check(lib.mpcg_active_scatter(C.byref(pr), B, _ptr(slot_of), C.byref(dio), C.byref(fio),
+                                   C.c_void_p(s.cuda_stream)), "mpcg_active_scatter")
+
+
+class ActiveWorkspace:
+    """mpcg_active_ws: the dense buffers, the plan and the pinned count of mpcg_solve_active for up to
+    max_batch solves of `pr`, on the current device."""
+
+    def __init__(self, pr: MpcgProblem, max_batch: int, with_lam: bool = False, with_qp: bool = False,
+                 with_stats: bool = False):
+        self.pr, self.max_batch = pr, int(max_batch)
+        self.with_lam, self.with_qp, self.with_stats = bool(with_lam), bool(with_qp), bool(with_stats)
+        self._c = lib.mpcg_active_ws_create(C.byref(pr), self.max_batch, int(self.with_lam), int(self.with_qp),
+                                            int(self.with_stats))
+        if not self._c:
+            raise RuntimeError(f"mpcg_active_ws_create failed: {last_error()}")
+
+    def close(self):
+        if self._c:
+            lib.mpcg_active_ws_destroy(self._c)
+            self._c = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def solve_active_device(pr: MpcgProblem, params, warm, xinit, enabled, ws=None, stream=None, lam_in=None,
+                        lam_out=False, qp_in=None, qp_out=False, stats=False, out=None):
+    """mpcg_solve_active (include/mpcg_active.h): solve_batch_device for the solves with enabled (B,) uint8
+    non-zero only -- plan, gather, one mpcg_solve of the dense batch, scatter; every other solve holds the
+    header's fill (exit ACTIVE_EXIT_SKIPPED).  ws: an ActiveWorkspace (None: one is created for this call).
+    Returns solve_batch_device's dict plus n_active (int) and slot_of (B,) int32.  Synchronises `stream`
+    once (the count is read on the host; not capturable into a graph) and returns with the solve and the
+    scatter in flight on it."""
+    import torch
+
+    B = params.shape[0]
+    N, nx, NU = pr.N, pr.nx, pr.nu
+    LS = lam_stride(pr)
+    dev = params.device
+    for t_, shape in ((params, (B, N, pr.npar)), (warm, (B, N + 1, NU + nx)), (xinit, (B, nx))):
+        assert t_.dtype == torch.float64 and t_.is_cuda and t_.is_contiguous() and tuple(t_.shape) == shape, \
+            (tuple(t_.shape), shape)
+    assert enabled.dtype == torch.uint8 and enabled.is_cuda and enabled.is_contiguous() and enabled.numel() == B
+    if lam_in is not None:
+        assert tuple(lam_in.shape) == (B, N, LS) and lam_in.is_contiguous() and lam_in.dtype == torch.float64
+    own = ws is None
+    if own:
+        ws = ActiveWorkspace(pr, max(B, 1), with_lam=lam_in is not None or lam_out,
+                             with_qp=qp_in is not None or qp_out, with_stats=stats)
+    if out is None:
+        out = dict(xtraj=torch.empty((B, N + 1, nx), dtype=torch.float64, device=dev),
+                   utraj=torch.empty((B, N, NU), dtype=torch.float64, device=dev),
+                   pobj=torch.empty((B,), dtype=torch.float64, device=dev),
+                   exit=torch.empty((B,), dtype=torch.int32, device=dev),
+                   info=torch.empty((B, INFO_STRIDE), dtype=torch.int32, device=dev))
+    if lam_out and "lam" not in out:
+        out["lam"] = torch.empty((B, N, LS), dtype=torch.float64, device=dev)
+    Q = qp_mem_size(pr) if (qp_in is not None or qp_out) else 0
+    if qp_in is not None:
+        assert tuple(qp_in.shape) == (B, Q) and qp_in.is_contiguous() and qp_in.dtype == torch.float64
+    if qp_out and "qp" not in out:
+        out["qp"] = torch.empty((B, Q), dtype=torch.float64, device=dev)
+    if stats and "stats" not in out:
+        out["stats"] = torch.empty((B, STATS_STRIDE), dtype=torch.float64, device=dev)
+    if "slot_of" not in out:
+        out["slot_of"] = torch.empty((B,), dtype=torch.int32, device=dev)
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    io = MpcgIo(params.data_ptr(), warm.data_ptr(), xinit.data_ptr(),
+                None if lam_in is None else lam_in.data_ptr(),
+                out["xtraj"].data_ptr(), out["utraj"].data_ptr(), out["pobj"].data_ptr(), out["exit"].data_ptr(),
+                out["info"].data_ptr() if out.get("info") is not None else None,
+                out["lam"].data_ptr() if lam_out else None,
+                None if qp_in is None else qp_in.data_ptr(),
+                out["qp"].data_ptr() if qp_out else None,
+                out["stats"].data_ptr() if stats else None)
+    n = C.c_int(-1)
+    try:
+        _check(lib.mpcg_solve_active(C.byref(pr), B, C.byref(io), _ptr(enabled), ws._c, C.byref(n),
+                                     C.c_void_p(s.cuda_stream)), "mpcg_solve_active")
+        _check(lib.mpcg_active_ws_read_plan(ws._c, B, _ptr(out["slot_of"]), None, C.c_void_p(s.cuda_stream)),
+               "mpcg_active_ws_read_plan")
+    finally:
+        if own:
+            # the workspace's buffers are read by work still in flight
+            s.synchronize()
+            ws.close()
+    out["n_active"] = int(n.value)
+    return out

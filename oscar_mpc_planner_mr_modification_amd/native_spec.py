@@ -229,3 +229,8 @@ GUIDANCE_MAX_N, GUIDANCE_MAX_ELL, GUIDANCE_MAX_SEG = 32, 32, 8
 GUIDANCE_ACCEL, GUIDANCE_RELEVANT, GUIDANCE_OFFSET, GUIDANCE_WIDTH, GUIDANCE_ONSET = 1.0, 2.5, 1.2, 2.0, 0.8
 GUIDANCE_PUSH_MARGIN, GUIDANCE_CLEARANCE, GUIDANCE_V_FLOOR = 0.75, 0.25, 1e-3
 GUIDANCE_EXIT_DISABLED = -100
+
+# the active-solve compaction (include/mpcg_active.h), exported from the same library
+ACTIVE_EXPORTS = ("mpcg_active_plan", "mpcg_active_gather", "mpcg_active_scatter", "mpcg_active_ws_create",
+                  "mpcg_active_ws_destroy", "mpcg_active_ws_read_plan", "mpcg_solve_active")
+ACTIVE_EXIT_SKIPPED = -100

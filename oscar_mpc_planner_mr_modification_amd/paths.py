@@ -265,7 +265,8 @@ class PathLoop:
     Guidance trajectories and obstacle predictions still come from outside (`loop.set_scene_data`,
     or a `FleetLoop`'s launches around the same scenes), unless the loop has a guidance layer
     (loop_options guidance_layer=guidance.GuidanceLayer): the path update runs before the layer's
-    update inside ControlLoop.step, because the layer's nominal needs this step's window."""
+    update inside ControlLoop.step, because the layer's nominal needs this step's window.  With the
+    layer, loop_options skip_disabled=True leaves the planners it disables unsolved."""
 
     def __init__(self, layout, scenes, table: PathTable, path_of, device, settings: PathSettings, robot_radius: float,
                  w_consistency: float, selection_weight: float, spline_slot: int | None = None, **loop_options):
