@@ -390,19 +390,9 @@ __device__ inline void erk_unicycle(const mpcg_problem& pr, const double z[NU + 
 // the convergence test exactly as in the full-size sweep)
 // NA: the leading NA x NA block of the NZ x NZ array is mirrored in place
 // (NA < NZ: the trailing rows / columns are decoupled and handled by the caller)
-// MPCG_MIRROR_RR=1: the round-robin (parallel) Jacobi ordering below, A/B only -- measured slower
-// (profiles/r03q_ab.jsonl: C2 11.97 -> 12.04 ms, C1 +1.6 %, C5 +1.3 %, JS +1.2 %; C4 -1.0 %) and its
-// different rounding moved one C5 copy of 8,192 to another exit (1602: QP failure in the oracle,
-// success on the GPU; profiles/r03q_rr_fullsize.log)
-#ifndef MPCG_MIRROR_RR
-#define MPCG_MIRROR_RR 0
-#endif
-// round-robin schedule of n (even) players: pair i of round r (players n - 1 and r, then
-// (r + i, r - i) mod n - 1), lower / higher index
-__host__ __device__ constexpr int rr_a(int n, int r, int i) { return i == 0 ? n - 1 : (r + i) % (n - 1); }
-__host__ __device__ constexpr int rr_b(int n, int r, int i) { return i == 0 ? r : (r - i + n - 1) % (n - 1); }
-__host__ __device__ constexpr int rr_lo(int n, int r, int i) { return rr_a(n, r, i) < rr_b(n, r, i) ? rr_a(n, r, i) : rr_b(n, r, i); }
-__host__ __device__ constexpr int rr_hi(int n, int r, int i) { return rr_a(n, r, i) < rr_b(n, r, i) ? rr_b(n, r, i) : rr_a(n, r, i); }
+// (The round-robin, parallel Jacobi ordering measured slower -- profiles/r03q_ab.jsonl: C2 11.97 -> 12.04
+// ms, C1 +1.6 %, C5 +1.3 %, JS +1.2 %; C4 -1.0 % -- and its different rounding moved one C5 copy of 8,192
+// to another exit, 1602: QP failure in the oracle, success on the GPU; profiles/r03q_rr_fullsize.log)
 template <int NZ, int NA = NZ>
 __device__ inline void mirror(double A[NZ][NZ], double eps, double dia_extra = 0.0) {
     // Cyclic Jacobi on the symmetric part, one-sided rotation updates on the
@@ -427,58 +417,6 @@ __device__ inline void mirror(double A[NZ][NZ], double eps, double dia_extra = 0
             for (int j = i + 1; j < NA; ++j) off += A[i][j] * A[i][j];
         }
         if (off <= 1e-32 * dia || off < 1e-300) break;
-#if MPCG_MIRROR_RR
-        // round-robin (parallel) ordering: the pairs of a round are disjoint, so their rotation
-        // parameters depend only on the round's starting entries and their reciprocal / square
-        // root chains run side by side; the rotations are then applied one after the other
-        constexpr int NPL = NA + (NA & 1), NPR = NPL / 2;
-#pragma unroll
-        for (int rd = 0; rd < NPL - 1; ++rd) {
-            double tr[NPR], snr[NPR], taur[NPR];
-            bool on[NPR];
-#pragma unroll
-            for (int i = 0; i < NPR; ++i) {
-                const int p = rr_lo(NPL, rd, i), q = rr_hi(NPL, rd, i);
-                on[i] = false;
-                if (q >= NA) continue;  // the bye of an odd count
-                const double apq = A[p][q];
-                on[i] = fabs(apq) >= 1e-300;
-                const double theta = 0.5 * (A[q][q] - A[p][p]) * frcp(on[i] ? apq : 1.0);
-                const double at = fabs(theta);
-                double t = at < 1e150 ? frcp(at + fsqrt_pos(fma(at, at, 1.0))) : 0.5 * frcp(at);
-                t = theta >= 0.0 ? t : -t;
-                const double c = frsq(fma(t, t, 1.0));
-                tr[i] = t;
-                snr[i] = t * c;
-                taur[i] = snr[i] * frcp(1.0 + c);
-            }
-#pragma unroll
-            for (int i = 0; i < NPR; ++i) {
-                const int p = rr_lo(NPL, rd, i), q = rr_hi(NPL, rd, i);
-                if (q >= NA || !on[i]) continue;
-                const double apq = A[p][q], t = tr[i], sn = snr[i], tau = taur[i];
-                A[p][p] -= t * apq;
-                A[q][q] += t * apq;
-                A[p][q] = 0.0;
-#pragma unroll
-                for (int r = 0; r < NA; ++r) {
-                    if (r == p || r == q) continue;
-                    double& arp = r < p ? A[r][p] : A[p][r];
-                    double& arq = r < q ? A[r][q] : A[q][r];
-                    const double g = arp, h = arq;
-                    arp = g - sn * fma(g, tau, h);
-                    arq = h + sn * fma(-h, tau, g);
-                }
-#pragma unroll
-                for (int r = 0; r < NA; ++r) {
-                    const double g = V[r][p], h = V[r][q];
-                    V[r][p] = g - sn * fma(g, tau, h);
-                    V[r][q] = h + sn * fma(-h, tau, g);
-                }
-            }
-        }
-        continue;
-#endif
 #pragma unroll
         for (int p = 0; p < NA - 1; ++p)
 #pragma unroll
@@ -513,83 +451,6 @@ __device__ inline void mirror(double A[NZ][NZ], double eps, double dia_extra = 0
                 }
             }
     }
-    double d[NA];
-#pragma unroll
-    for (int i = 0; i < NA; ++i) {
-        double di = A[i][i];
-        d[i] = (di >= -eps && di <= eps) ? eps : fabs(di);
-    }
-#pragma unroll
-    for (int i = 0; i < NA; ++i)
-#pragma unroll
-        for (int j = i; j < NA; ++j) {
-            double acc = 0.0;
-#pragma unroll
-            for (int k = 0; k < NA; ++k) acc += V[i][k] * d[k] * V[j][k];
-            A[i][j] = acc;
-            A[j][i] = acc;
-        }
-}
-
-// The sweeps of mirror() with the eigenvector rows split over the PARTS lanes of a stage: every
-// part applies the same rotations to its own copy of A (symmetrised upper triangle, from the
-// stage's part 0), and part p accumulates only the rows p, p + PARTS, ... of V (Vr[t] = row
-// p + PARTS t; rows past NA stay unused).  Per entry the operations of mirror(): bit-identical.
-template <int NZ, int NA, int PARTS>
-__device__ inline void mirror_rows(double A[NZ][NZ], double (&Vr)[(NA + PARTS - 1) / PARTS][NA], int part,
-                                   double dia_extra) {
-    constexpr int RV = (NA + PARTS - 1) / PARTS;
-#pragma unroll
-    for (int t = 0; t < RV; ++t)
-#pragma unroll
-        for (int j = 0; j < NA; ++j) Vr[t][j] = (part + PARTS * t == j) ? 1.0 : 0.0;
-    for (int sweep = 0; sweep < 50; ++sweep) {
-        double off = 0.0, dia = 0.0;
-#pragma unroll
-        for (int i = 0; i < NA; ++i) {
-            dia += A[i][i] * A[i][i];
-            if (i == NA - 1) dia += dia_extra;
-#pragma unroll
-            for (int j = i + 1; j < NA; ++j) off += A[i][j] * A[i][j];
-        }
-        if (off <= 1e-32 * dia || off < 1e-300) break;
-#pragma unroll
-        for (int p = 0; p < NA - 1; ++p)
-#pragma unroll
-            for (int q = p + 1; q < NA; ++q) {
-                const double apq = A[p][q];
-                if (fabs(apq) >= 1e-300) {
-                    const double theta = 0.5 * (A[q][q] - A[p][p]) * frcp(apq);
-                    const double at = fabs(theta);
-                    double t = at < 1e150 ? frcp(at + fsqrt_pos(fma(at, at, 1.0))) : 0.5 * frcp(at);
-                    t = theta >= 0.0 ? t : -t;
-                    const double c = frsq(fma(t, t, 1.0)), sn = t * c;
-                    const double tau = sn * frcp(1.0 + c);
-                    A[p][p] -= t * apq;
-                    A[q][q] += t * apq;
-                    A[p][q] = 0.0;
-#pragma unroll
-                    for (int r = 0; r < NA; ++r) {
-                        if (r == p || r == q) continue;
-                        double& arp = r < p ? A[r][p] : A[p][r];
-                        double& arq = r < q ? A[r][q] : A[q][r];
-                        const double g = arp, h = arq;
-                        arp = g - sn * fma(g, tau, h);
-                        arq = h + sn * fma(-h, tau, g);
-                    }
-#pragma unroll
-                    for (int r = 0; r < RV; ++r) {
-                        const double g = Vr[r][p], h = Vr[r][q];
-                        Vr[r][p] = g - sn * fma(g, tau, h);
-                        Vr[r][q] = h + sn * fma(-h, tau, g);
-                    }
-                }
-            }
-    }
-}
-// mirror()'s reconstruction A = V diag(f(d)) V' from the eigenvalues on A's diagonal
-template <int NZ, int NA>
-__device__ inline void mirror_rebuild(double A[NZ][NZ], const double (&V)[NA][NA], double eps) {
     double d[NA];
 #pragma unroll
     for (int i = 0; i < NA; ++i) {

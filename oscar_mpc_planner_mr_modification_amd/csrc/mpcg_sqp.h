@@ -99,14 +99,11 @@ struct Cfg {
     static constexpr int NH = NL + NE + NS;
     static constexpr int NTRI = NZ * (NZ + 1) / 2;  // packed stage block
     static constexpr int NPT = NX * (NX + 1) / 2;   // packed cost-to-go
-#ifndef MPCG_P_PAD
-#define MPCG_P_PAD 1
-#endif
     // cost-to-go rows padded to an even count of doubles: every stage's broadcast read is
     // 16-B aligned (ds_read_b128 with immediate offsets instead of ds_read2_b64 on every
     // other stage): C2 12.49 -> 12.26 ms, C5 20.51 -> 19.93.  Not on the long horizons
     // (C4 measured 53.84 -> 54.19) nor on the compact C3 storage (at its occupancy line)
-    static constexpr int NPTP = (MPCG_P_PAD && MODEL_ != 1 && (64 / (N_ + 1)) >= 3) ? NPT + (NPT & 1) : NPT;
+    static constexpr int NPTP = (MODEL_ != 1 && (64 / (N_ + 1)) >= 3) ? NPT + (NPT & 1) : NPT;
     // h rows touch (x, y, psi) and, with the slack model, the slack state:
     // the barrier block of the h rows is NB x NB on those variables
     static constexpr int NB = (HAS_SLACK && NS > 0) ? 4 : 3;
@@ -125,14 +122,8 @@ struct Cfg {
     // work-queue launch (sqp_kernel): the N <= 20 three-part unicycle instances (C1, C2, C5).  On the
     // long horizons the loop around the solve moves the register allocation into scratch (C4 132 ->
     // 840 B/lane, 44.3 -> 71.3 ms; JS / JD 0 -> 456 / 528 B/lane, C3 552 -> 720), so they keep one
-    // workgroup per problem (MPCG_QUEUE_ALL / MPCG_NO_QUEUE: A/B)
-#if defined(MPCG_NO_QUEUE)
-    static constexpr bool QUEUE = false;
-#elif defined(MPCG_QUEUE_ALL)
-    static constexpr bool QUEUE = true;
-#else
+    // workgroup per problem
     static constexpr bool QUEUE = MODEL_ == 0 && PARTS_MAX == 3;
-#endif
     // rows of a lane: box slots j (variable part + PARTS j, lower and upper
     // side: slots 2j, 2j + 1), then h slots r (h row part + PARTS r)
     static constexpr int BVS = (NZ + PARTS - 1) / PARTS;
@@ -142,42 +133,26 @@ struct Cfg {
     // instances: C1, C2); C5 (14 slots), C3 (16) and C4 (20) recompute it, which keeps them out of
     // scratch.  Round 5: 14 -> 13, C5 stops storing it (with the HPIPM profile's cold start and
     // refinement test its stored 1/t pushed the residual and step passes into scratch, 232 -> 80
-    // B/lane; profiles/r05c_ab_st14_C5.jsonl).  MPCG_STORE_IT_MAX=0 recomputes it everywhere.
+    // B/lane; profiles/r05c_ab_st14_C5.jsonl).
     // Two-part instances (JS, JD) recompute it: a round-2 build that stored 1/t there computed wrong
     // trajectories and faulted once, and that fault's cause was never named (its build no longer
     // exists).  Round 5 built the stored form again on the shipped sources, ran full-size parity on JS
     // and JD without a fault (profiles/r05f_variant_storeit.jsonl) and lifted the gate for a 1.4 % JS
     // gain (52.45 -> 51.73 ms, profiles/r05f_ab_storeit.jsonl); one clean run shows the fault did not
     // recur, not that its cause is gone, so round 6 restores the gate.  -DMPCG_STORE_IT_ANY
-    // (or MPCG_STORE_IT_MAX2 > 0) builds the stored form on two-part instances for A/B runs only.
-#ifndef MPCG_STORE_IT_MAX
-#define MPCG_STORE_IT_MAX 13
-#endif
-#ifndef MPCG_STORE_IT_MAX2
+    // builds the stored form on two-part instances (up to 12 slots) for A/B runs only.
 #ifdef MPCG_STORE_IT_ANY
-#define MPCG_STORE_IT_MAX2 12
+    static constexpr bool STORE_IT_ANY = true;
 #else
-#define MPCG_STORE_IT_MAX2 0
+    static constexpr bool STORE_IT_ANY = false;
 #endif
-#endif
-    static constexpr bool STORE_IT = SLOTS <= (PARTS == 3 ? MPCG_STORE_IT_MAX : MPCG_STORE_IT_MAX2);
-    // box bounds selected per use instead of held in registers (LaneBounds; MPCG_BOUNDS_SEL=1, A/B
-    // only): C2 went into scratch with it (0 -> 68 B/lane), C3 unchanged, and C4 (148 -> 132 B/lane
-    // of scratch) measured 50.75 vs 50.72 ms in two alternating repetitions (profiles/r03k_ab.jsonl)
-#ifndef MPCG_BOUNDS_SEL
-#define MPCG_BOUNDS_SEL 0
-#endif
-    static constexpr bool BOUNDS_SEL = MPCG_BOUNDS_SEL > 0;
+    static constexpr bool STORE_IT = SLOTS <= (PARTS == 3 ? 13 : STORE_IT_ANY ? 12 : 0);
     static constexpr int NBOX = 2 * NU + 2 * NX;  // box rows of a stage in 1..N-1 (input + state bounds)
     // Linear rows (topology and scenario halfspaces) read their coefficients from the
     // parameter block instead of LDS, and their gaps are recomputed from the iterate:
     // only the ellipsoid rows keep gradients / gaps in LDS.  Used where it lowers the
     // LDS footprint below an occupancy step (C5: 51.6 -> 36.6 KB, 3 -> 4 solves per CU).
-#ifdef MPCG_LIN_PARAMS_ALL
-    static constexpr bool LIN_PARAMS = true;  // occupancy experiments: the compact row storage everywhere
-#else
     static constexpr bool LIN_PARAMS = NS > 0 || N >= 30;
-#endif
     // gradient components kept per LDS row: with LIN_PARAMS the psi component is
     // rebuilt from (x, y) components and the stage's disc-offset derivatives
     static constexpr int DGC = LIN_PARAMS ? 2 : 3;
@@ -208,51 +183,29 @@ struct Cfg {
     // rows shrink the per-solve block 15.3 -> 10.3 KB: 52.85 -> 51.26 ms, 304.5k -> 314.0k solves/s
     // (profiles/r02v_ab_*_C4.json; at three solves per CU, before GFH, it was 2.6 % slower).  On
     // N 20 the constant rows changed the register allocation into scratch (C2 0 -> 128 B/lane).
-    // (MPCG_FCONST_N=20, A/B: the N 20 instances with the constant rows and their hoisting went into
-    // scratch and ran slower -- C2 11.97 -> 13.34 ms, C5 19.46 -> 25.71, C1 10.43 -> 11.21;
+    // (A build with the constant rows and their hoisting on the N 20 instances too went into scratch
+    // and ran slower -- C2 11.97 -> 13.34 ms, C5 19.46 -> 25.71, C1 10.43 -> 11.21;
     // profiles/r03q_ab.jsonl)
-#ifndef MPCG_FCONST_N
-#define MPCG_FCONST_N 30
-#endif
-    static constexpr bool FCONST = MODEL_ == 0 && N_ >= MPCG_FCONST_N;
+    static constexpr bool FCONST = MODEL_ == 0 && N_ >= 30;
     static constexpr int NFR = COMPACT ? 4 : (FCONST ? 2 : NX), NFC = COMPACT ? NZ - 1 : NZ;
     static constexpr int NHP = COMPACT ? (NZ - 1) * NZ / 2 + 1 : NTRI;
     // the vector chains split over the parts of a stage (rows of the backward map, columns of
     // the forward one); the register-starved bicycle instance keeps one owner per stage
-#ifndef MPCG_C3_SPLIT
-#define MPCG_C3_SPLIT 0
-#endif
-#ifndef MPCG_C3_FACFLAT
-#define MPCG_C3_FACFLAT 0
-#endif
-    static constexpr bool CHAIN_SPLIT = !COMPACT || MPCG_C3_SPLIT;
+    static constexpr bool CHAIN_SPLIT = !COMPACT;
     // the split chains as two-stage composed maps (half the sequential steps; see the
     // vector passes in sqp_kernel).  Measured against the one-step chains: JS 43.45 ->
     // 42.20 ms; C2 12.74 -> 13.09, C4 53.34 -> 53.78, C5 19.49 -> 20.07 (the compositions
     // and the extra live state cost more than the halved chain there), so only the long
-    // horizons with the constant-row storage use them.  MPCG_PAIR_ALL / MPCG_NO_PAIR: A/B.
-#if defined(MPCG_NO_PAIR)
-    static constexpr bool PAIR_WANTED = false;
-#elif defined(MPCG_PAIR_ALL)
-    static constexpr bool PAIR_WANTED = true;
-#else
+    // horizons with the constant-row storage use them.
     static constexpr bool PAIR_WANTED = FCONST && NE_ <= 8;
-#endif
     static constexpr bool PAIR_CHAINS = PAIR_WANTED && CHAIN_SPLIT && (N_ + 1) / 2 * NX_ * NX_ <= (N_ + 1) * NDH &&
                                         (N_ + 1) / 2 * NX_ <= 128;
     // branch-free Riccati step (every lane, prefetch after the pivot reads, pivot failures
     // voted from a register)
-    static constexpr bool FAC_FLAT = !COMPACT || MPCG_C3_FACFLAT;
-#ifndef MPCG_REC_P2
-#define MPCG_REC_P2 0
-#endif
+    static constexpr bool FAC_FLAT = !COMPACT;
     // branch-free chain records (three parts per stage: C2 13.40 -> 12.92 ms, C5 23.45 -> 22.75;
     // the two-part long horizon C4 spills with it, 56.4 -> 76.2 ms)
-#ifdef MPCG_REC_SELECT
     static constexpr bool REC_FLAT = CHAIN_SPLIT && PARTS == 3;
-#else
-    static constexpr bool REC_FLAT = CHAIN_SPLIT && (PARTS == 3 || MPCG_REC_P2);
-#endif
     // RES_CARRY: the refinement test's pass (HPIPM's profile) evaluates H dz, F' pi and F dz + b - dz+ at the
     // trial point dz + ddz on the stage blocks it has just read; the residual pass that follows evaluates
     // the same products on the same blocks at dz + alpha ddz, and alpha is known before the test.  With the
@@ -341,44 +294,22 @@ struct Lds {
 };
 
 // four solves per CU need at most a quarter of the CU's 160 KiB of LDS per workgroup
-// (MPCG_LDS_SOLVES_PER_CU, occupancy experiments only: another LDS line -- 8 for two waves per SIMD
-// -- and the smallest storage that gets under it)
-#ifdef MPCG_LDS_SOLVES_PER_CU
-constexpr size_t LDS_QUARTER = 160 * 1024 / MPCG_LDS_SOLVES_PER_CU;
-constexpr bool LDS_SMALLEST = true;
-#else
 constexpr size_t LDS_QUARTER = 160 * 1024 / 4;
-constexpr bool LDS_SMALLEST = false;
-#endif
 template <class C>
 __host__ __device__ constexpr bool lds_lean() {
-    if (LDS_SMALLEST) return C::COMPACT || sizeof(Lds<C, false>) > LDS_QUARTER;
     return C::COMPACT || (sizeof(Lds<C, false>) > LDS_QUARTER && sizeof(Lds<C, true>) <= LDS_QUARTER);
 }
 template <class C>
 __host__ __device__ constexpr bool lds_gfh() {
-#ifdef MPCG_NO_GFH
-    return false;
-#else
-    if (LDS_SMALLEST) return sizeof(Lds<C, lds_lean<C>(), false>) > LDS_QUARTER;
     return sizeof(Lds<C, lds_lean<C>(), false>) > LDS_QUARTER && sizeof(Lds<C, lds_lean<C>(), true>) <= LDS_QUARTER;
-#endif
 }
-// conflict-minimal strides where they fit under the line (MPCG_NO_STRIDE_PAD: A/B)
+// conflict-minimal strides where they fit under the line
 template <class C>
 __host__ __device__ constexpr int lds_pad() {
-#if defined(MPCG_NO_STRIDE_PAD)
-    return 0;
-#else
-#if defined(MPCG_NO_P_ALIGN)
-    constexpr bool P_ALIGN = false;
-#else
     constexpr bool P_ALIGN = !C::COMPACT;  // C3 with 21 -> 22: 21.14 -> 21.40 ms (profiles/r03n_ab.jsonl)
-#endif
     return P_ALIGN && sizeof(Lds<C, lds_lean<C>(), lds_gfh<C>(), 2>) <= LDS_QUARTER ? 2
            : sizeof(Lds<C, lds_lean<C>(), lds_gfh<C>(), 1>) <= LDS_QUARTER         ? 1
                                                                                    : 0;
-#endif
 }
 template <class C>
 using LdsOf = Lds<C, lds_lean<C>(), lds_gfh<C>(), lds_pad<C>()>;
@@ -394,36 +325,10 @@ template <class C>
 __host__ __device__ constexpr size_t itref_doubles() {
     return 2 * (size_t)(C::N + 1) * C::NZ + (size_t)C::N * C::NX;
 }
-// The split launch (MPCG_SPLIT): the lean SQP-RTI as one linearisation
-// kernel and one interior-point kernel per RTI iteration instead of the fused loop, each compiled for
-// its phase alone.  Bit 0: split every lean instance; bit 1: the interior-point launches take the work
-// queue; bit 2: the linearisation launches do.  (A/B build only.)
-#ifndef MPCG_SPLIT
-#define MPCG_SPLIT 0
-#endif
-enum { MODE_FUSED = 0, MODE_LIN = 1, MODE_QP = 2 };
-template <class C>
-__host__ __device__ constexpr bool split_on() {
-    return (MPCG_SPLIT & 1) != 0;
-}
-// the block one split launch hands the next for a solve (global, after the refinement scratch): the
-// iterate (z, pi), the linearisation (g, b, the h rows' gradients, gaps and offsets; [B A] and H unless
-// GFH keeps them in the workspace already), the rows' NLP multipliers lane-major, and the counters
-template <class C>
-struct Carry {
-    using L = LdsOf<C>;
-    static constexpr size_t Z = 0, PI = Z + sizeof(L::z) / 8, G = PI + sizeof(L::pi_nlp) / 8,
-                            B = G + sizeof(L::g) / 8, DG = B + sizeof(L::b) / 8, HD = DG + sizeof(L::Dg) / 8,
-                            DISC = HD + sizeof(L::hd) / 8, H = DISC + sizeof(L::disc) / 8,
-                            F = H + (lds_gfh<C>() ? 0 : sizeof(L::H) / 8),
-                            NLAM = F + (lds_gfh<C>() ? 0 : sizeof(L::F) / 8), META = NLAM + 64 * (size_t)C::HS,
-                            SIZE = META + 8;
-    // META: res_eq, done, acados_status, qp_status, sqp_iter, qp_total, n_maxit
-};
-// one solve's global workspace: the GFH blocks, then the refinement scratch (then the split's carry)
+// one solve's global workspace: the GFH blocks, then the refinement scratch
 template <class C>
 __host__ __device__ constexpr size_t ws_doubles() {
-    return gfh_doubles<C>() + itref_doubles<C>() + (split_on<C>() ? Carry<C>::SIZE : 0);
+    return gfh_doubles<C>() + itref_doubles<C>();
 }
 
 // Diagnostic per-phase cycle stamps (separate build with -DMPCG_STAMPS; the
@@ -452,35 +357,12 @@ __host__ __device__ constexpr size_t ws_doubles() {
 #define STAMP_STORE(ptr, sol) do {} while (0)
 #endif
 
-// Unrolling of the stage loops of the interior point: the Riccati recursion (MPCG_UNROLL_FAC) and the split
-// vector chains (MPCG_UNROLL_CHAIN).  Default: fully unrolled (every stage's addresses, lane masks and
-// readlane lanes literal).  MPCG_FAC_UNROLL / MPCG_CHAIN_UNROLL = n: unrolled by n (1: a rolled loop with
-// run-time stage offsets), for A/B runs of the instruction footprint.
-#define MPCG_PRAGMA_(x) _Pragma(#x)
-#ifdef MPCG_FAC_UNROLL
-#define MPCG_UNROLL_FAC MPCG_PRAGMA_(unroll MPCG_FAC_UNROLL)
-#else
-#define MPCG_UNROLL_FAC MPCG_PRAGMA_(unroll)
-#endif
-#ifdef MPCG_CHAIN_UNROLL
-#define MPCG_UNROLL_CHAIN MPCG_PRAGMA_(unroll MPCG_CHAIN_UNROLL)
-#else
-#define MPCG_UNROLL_CHAIN MPCG_PRAGMA_(unroll)
-#endif
-
 // One wavefront per workgroup (blockDim 64): the lanes exchange data through LDS,
 // and a wave's LDS instructions execute in issue order, so an exchange needs a
 // compiler barrier only, not an s_waitcnt on the producing stores before the
-// consuming loads issue (-DMPCG_LDS_WAIT restores __syncthreads for A/B runs).
-__device__ __forceinline__ void wave_sync() {
-#ifdef MPCG_LDS_WAIT
-    __syncthreads();
-#else
-    __asm__ volatile("" ::: "memory");
-#endif
-}
+// consuming loads issue.
+__device__ __forceinline__ void wave_sync() { __asm__ volatile("" ::: "memory"); }
 
-#ifndef MPCG_REC_SELECT
 typedef __attribute__((address_space(3))) double lds_double;
 // lanes in MASK get `on`, the others `off` (a literal lane mask: no per-step compare and no
 // precomputed per-step addresses kept in registers)
@@ -491,7 +373,6 @@ __device__ __forceinline__ unsigned sel_lanes(unsigned long long mask, unsigned 
 }
 __device__ __forceinline__ unsigned lds_addr(double* p) { return (unsigned)(size_t)(lds_double*)p; }
 __device__ __forceinline__ void lds_store(unsigned a, double v) { *(lds_double*)(size_t)a = v; }
-#endif
 __device__ __forceinline__ double readlane_d(double v, int lane) {
     const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane);
     const int hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
@@ -505,22 +386,13 @@ __device__ __forceinline__ double dpp_d(double v) {
     return __hiloint2double(hi, lo);
 }
 // value of lane + p (p = 1, 2: the other parts of a stage) for part 0's fold: DPP
-// whole-wave shifts (wave_shl:1) instead of ds_bpermute (-DMPCG_FOLD_BPERMUTE restores it)
+// whole-wave shifts (wave_shl:1) instead of ds_bpermute
 __device__ __forceinline__ double lane_down(double v, int p) {
-#ifdef MPCG_FOLD_BPERMUTE
-    return __shfl_down(v, p);
-#else
     double w = dpp_d<0x130>(v);
     if (p == 2) w = dpp_d<0x130>(w);
     return w;
-#endif
 }
 __device__ __forceinline__ double wave_max(double v) {
-#ifdef MPCG_MAX_BPERMUTE
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
-    return v;
-#else
     // max is exact in any order: a DPP tree (quads, half rows, rows, then row 15 /
     // row 31 broadcasts) instead of six ds_bpermute levels, lane 63 broadcast
     v = fmax(v, dpp_d<0xB1>(v));        // quad_perm [1,0,3,2]
@@ -530,7 +402,6 @@ __device__ __forceinline__ double wave_max(double v) {
     v = fmax(v, dpp_d<0x142, 0xA>(v));  // row_bcast15 -> rows 1, 3
     v = fmax(v, dpp_d<0x143, 0xC>(v));  // row_bcast31 -> rows 2, 3
     return readlane_d(v, 63);
-#endif
 }
 __device__ __forceinline__ double wave_sum(double v) {
     // the same DPP tree as wave_max: every lane gets lane 63's sum, so the result is
@@ -545,28 +416,13 @@ __device__ __forceinline__ double wave_sum(double v) {
 }
 
 
-// One step of a split vector chain: h + G . v.  MPCG_CHAIN_TREE: two partial sums (the first
-// half of the terms from h, the second from 0) joined by one add, so the step's dependent chain is
-// ceil(n/2) + 1 operations deep instead of n (the chains are latency-bound at one wave per SIMD)
-#ifndef MPCG_CHAIN_TREE
-#define MPCG_CHAIN_TREE 0
-#endif
+// One step of a split vector chain: h + G . v, one dependent chain of n operations
 template <int n>
 __device__ __forceinline__ double chain_dot(double h, const double* G, const double* v) {
-    if constexpr (MPCG_CHAIN_TREE) {
-        constexpr int m = (n + 1) / 2;
-        double a = h, b = G[m] * v[m];
+    double a = h;
 #pragma unroll
-        for (int j = 0; j < m; ++j) a += G[j] * v[j];
-#pragma unroll
-        for (int j = m + 1; j < n; ++j) b += G[j] * v[j];
-        return a + b;
-    } else {
-        double a = h;
-#pragma unroll
-        for (int j = 0; j < n; ++j) a += G[j] * v[j];
-        return a;
-    }
+    for (int j = 0; j < n; ++j) a += G[j] * v[j];
+    return a;
 }
 
 // barrier contribution at (i, j), i >= j: diagonal part dh[0..nz) plus the
@@ -595,32 +451,16 @@ struct Rows {
 
 // The rows of the lane (stage k, part p): box slot j <-> variable v(j) = p + PARTS j,
 // h slot r <-> h row hh(r) = p + PARTS r.
-// Cfg::BOUNDS_SEL: the box bounds of a lane's variables are selected from the uniform problem
-// arguments by the lane's part at each use (two v_cndmask per bound) instead of living in
-// 2 BVS VGPR pairs for the whole solve
-template <class C, bool SEL = C::BOUNDS_SEL>
+// The box bounds of a lane's variables live in 2 BVS VGPR pairs for the whole solve.  (The select
+// form -- the bounds picked from the uniform problem arguments by the lane's part at each use, two
+// v_cndmask per bound -- spilled on C2, 0 -> 68 B/lane, left C3 unchanged, and on C4 (148 -> 132
+// B/lane of scratch) measured 50.75 vs 50.72 ms in two alternating repetitions; profiles/r03k_ab.jsonl)
+template <class C>
 struct LaneBounds {
     int k, part;
     double lo[C::BVS], hi[C::BVS];
     __device__ __forceinline__ double lo_at(int j) const { return lo[j]; }
     __device__ __forceinline__ double hi_at(int j) const { return hi[j]; }
-};
-template <class C>
-struct LaneBounds<C, true> {
-    int k, part;
-    const mpcg_problem* prb;
-    __device__ __forceinline__ static double bnd(const mpcg_problem& p, int v, bool upper) {
-        if (v >= C::NZ) return 0.0;
-        return v < C::NU ? (upper ? p.ubu[v] : p.lbu[v]) : (upper ? p.ubx[v - C::NU] : p.lbx[v - C::NU]);
-    }
-    __device__ __forceinline__ double sel(int j, bool upper) const {
-        double b = bnd(*prb, C::PARTS * j, upper);
-#pragma unroll
-        for (int q = 1; q < C::PARTS; ++q) b = part == q ? bnd(*prb, q + C::PARTS * j, upper) : b;
-        return b;
-    }
-    __device__ __forceinline__ double lo_at(int j) const { return sel(j, false); }
-    __device__ __forceinline__ double hi_at(int j) const { return sel(j, true); }
 };
 template <class C>
 struct LaneRows : LaneBounds<C> {
@@ -746,35 +586,27 @@ __host__ __device__ inline int qp_profile_kind(const mpcg_problem& pr) {
 #define MPCG_KERNEL_ATTR __launch_bounds__(64, 1)
 #endif
 // one solve `sol` on the calling wavefront (the body of sqp_kernel)
-template <class C, bool FULL, int PROF, int MODE>
+template <class C, bool FULL, int PROF>
 __device__ __forceinline__ void sqp_solve(mpcg_problem pr, int batch, mpcg_io io,
                                           unsigned long long* __restrict__ stamps, double* __restrict__ gws,
-                                          const int sol, const int split_it) {
+                                          const int sol) {
 #include "mpcg_sqp_body.inc"
 }
 
 // The batched solve.  queue == NULL or an instance without C::QUEUE: workgroup b solves problem b
-// (a grid of `batch` workgroups).  Otherwise a grid of at most the resident workgroups (launch_instance: MPCG_QUEUE) takes the
-// problems from the head of a work queue, queue[0], one at a time until it runs past `batch`:
+// (a grid of `batch` workgroups).  Otherwise a grid of at most the resident workgroups (queue_grid,
+// mpcg_instance.h) takes the problems from the head of a work queue, queue[0], one at a time until it runs past `batch`:
 // the hardware deals workgroups to the XCDs round robin and starts a new one only when a slot
 // frees, so with a grid of one workgroup per solve each XCD works through a fixed eighth of the
 // batch and every solve pays a workgroup launch; here a wave that finishes early takes the next
 // solve of the whole batch (the tail).  Every wave leaves the loop on its first
 // ticket >= batch.  launch_instance zeroes the queue words on the launch stream before every
 // launch, so no launch depends on how the previous one on the same workspace ended.
-// MODE (the split launch, split_on): MODE_LIN linearises RTI iteration split_it, MODE_QP solves its QP and
-// steps; the fused kernel (MODE_FUSED) runs the whole loop
-template <class C, int MODE>
-__host__ __device__ constexpr bool kernel_queue() {
-    return MODE == MODE_FUSED ? C::QUEUE : MODE == MODE_QP ? (MPCG_SPLIT & 2) != 0 : (MPCG_SPLIT & 4) != 0;
-}
-template <class C, bool FULL = false, int PROF = PROF_RUNTIME, int MODE = MODE_FUSED>
+template <class C, bool FULL = false, int PROF = PROF_RUNTIME>
 __global__ MPCG_KERNEL_ATTR void sqp_kernel(mpcg_problem pr, int batch, mpcg_io io,
                                                     unsigned long long* __restrict__ stamps,
-                                                    double* __restrict__ gws, unsigned* __restrict__ queue,
-                                                    int split_it) {
-    static_assert(!(FULL && MODE != MODE_FUSED), "the full variant is not split");
-    if constexpr (!kernel_queue<C, MODE>()) {
+                                                    double* __restrict__ gws, unsigned* __restrict__ queue) {
+    if constexpr (!C::QUEUE) {
         (void)queue;
         const int sol = blockIdx.x;
 #include "mpcg_sqp_body.inc"
@@ -795,7 +627,7 @@ __global__ MPCG_KERNEL_ATTR void sqp_kernel(mpcg_problem pr, int batch, mpcg_io 
             return t < (unsigned)batch ? (int)t : batch;
         };
         for (int sol = q ? next() : (int)blockIdx.x; sol < batch; sol = q ? next() : batch) {
-            sqp_solve<C, FULL, PROF, MODE>(pr, batch, io, stamps, gws, sol, split_it);
+            sqp_solve<C, FULL, PROF>(pr, batch, io, stamps, gws, sol);
             wave_sync();
         }
     }

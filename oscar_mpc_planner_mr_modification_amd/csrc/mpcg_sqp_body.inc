@@ -13,20 +13,7 @@
     // loop and fold fewer per interior-point iteration (wasted only on the iteration that exits).
     // Measured (profiles/r03q_ab.jsonl, two alternating repetitions): C2 12.32 -> 11.97 ms, C1 10.61
     // -> 10.43, C4 47.48 -> 45.38, C5 20.60 -> 19.46, JS 38.32 -> 37.17; C3 20.30 -> 19.81
-    // (profiles/r03s_ab.jsonl).  (MPCG_FUSE_BAR=0: A/B)
-#ifndef MPCG_FUSE_BAR
-#define MPCG_FUSE_BAR 1
-#endif
-    constexpr bool FUSE_BAR = MPCG_FUSE_BAR > 0;
-#ifndef MPCG_COND
-#define MPCG_COND 1
-#endif
-#ifndef MPCG_ITREF
-#define MPCG_ITREF 1
-#endif
-#ifndef MPCG_MOVE
-#define MPCG_MOVE 1
-#endif
+    // (profiles/r03s_ab.jsonl).
     // RES_SPLIT: the stage algebra of the residual and barrier passes (H dz, the stationarity rows,
     // the Newton gradient, the dynamics rows) split over the parts of a stage -- part p owns the
     // rows of its box variables p, p + PARTS, ... (and dynamics rows p, p + PARTS, ...), whose box
@@ -36,51 +23,22 @@
     // horizons it moves the allocation into scratch (C4 45.29 -> 46.76, JD 40.45 -> 40.70, JS
     // 37.25 -> 37.13), so three-part instances only; and not on the slack model, where it was neutral
     // in time but moved the allocation into scratch (C5 52 -> 188 B/lane, 264 -> 782 MB of HBM traffic
-    // per launch, profiles/r03u_c5_pmc.json).  (MPCG_RES_SPLIT=0: off, 2: every instance)
-#ifndef MPCG_RES_SPLIT
-#define MPCG_RES_SPLIT 1
-#endif
-    constexpr bool RES_SPLIT = MPCG_RES_SPLIT > 0 && FUSE_BAR && !C::COMPACT && PARTS > 1 && 2 * NB <= NZ &&
-                               ((PARTS == 3 && NX == 5) || MPCG_RES_SPLIT > 1);
+    // per launch, profiles/r03u_c5_pmc.json).
+    constexpr bool RES_SPLIT = !C::COMPACT && 2 * NB <= NZ && PARTS == 3 && NX == 5;
     constexpr int DRS = (NX + PARTS - 1) / PARTS;  // dynamics rows per part
     static_assert(!(RES_SPLIT && LEAN), "the split passes read the dynamics multipliers from S.pin");
     // the next iterate's residual products formed in the refinement test's pass (C::RES_CARRY, mpcg_sqp.h):
     // the split passes only
-    constexpr bool RES_CARRY = C::RES_CARRY && RES_SPLIT && !LEAN && MPCG_ITREF > 0;
+    constexpr bool RES_CARRY = C::RES_CARRY && RES_SPLIT && !LEAN;
     // the centring pass of the conditional predictor-corrector (qp_cond_pred_corr) reads the predictor
     // products R.pr as zero through its flag instead of clearing them: a definition of the row state on
     // the way back around the phase loop costs the allocation.  Measured (profiles/r05o_ab.jsonl, bit for
     // bit the same results, profiles/r05o_bitcmp.jsonl): C4 344 -> 220 B/lane of scratch, 63.75 -> 60.68
     // ms; C2 15.23 -> 15.15; C5 80 -> 28 B/lane but 21.40 -> 21.49 ms; the LEAN instances (JS, JD, C3)
     // allocate worse with the flag (136 / 100 / 588 -> 152 / 108 / 636 B/lane).  So the unicycle without
-    // the slack state on its non-LEAN storage (C1, C2, C4).  (MPCG_CENTRED_FLAG=0 / 1: every instance one
-    // way, A/B)
-#if defined(MPCG_CENTRED_FLAG)
-    constexpr bool CFLAG = MPCG_CENTRED_FLAG > 0;
-#else
+    // the slack state on its non-LEAN storage (C1, C2, C4).
     constexpr bool CFLAG = !LEAN && !C::HAS_SLACK;
-#endif
-    // MIRROR's eigenvector rows split over the parts of a stage (MPCG_MSPLIT=1, A/B only): bit-identical
-    // outputs (scripts/bitcmp.py on C2, C5, C4, JS: profiles/r03t_bitcmp.log) but slower everywhere --
-    // the stage matrix and row exchanges and the longer-lived state push the linearisation into
-    // scratch: C2 11.65 -> 12.46 ms, C1 10.16 -> 10.45, C4 45.41 -> 50.57, C5 19.47 -> 21.53, JS
-    // 37.24 -> 39.63, JD 40.56 -> 43.38 (profiles/r03t_ab.jsonl)
-#ifndef MPCG_MSPLIT
-#define MPCG_MSPLIT 0
-#endif
-    constexpr bool MSPLIT = MPCG_MSPLIT > 0 && C::MODEL == 0;
-    // the feedback's new dynamics multipliers split over the parts too (MPCG_PIN_SPLIT=1, A/B only:
-    // measured slower, C2 11.69 -> 11.78 ms, C1 10.16 -> 10.22, C5 unchanged; profiles/r03s_ab.jsonl)
-#ifndef MPCG_PIN_SPLIT
-#define MPCG_PIN_SPLIT 0
-#endif
-    constexpr bool PIN_SPLIT = MPCG_PIN_SPLIT > 0 && RES_SPLIT && !LEAN && C::CHAIN_SPLIT;
     __shared__ LdsOf<C> S;
-#ifdef MPCG_LDS_PAD
-    // occupancy experiment only: pad the LDS footprint
-    __shared__ char lds_pad[MPCG_LDS_PAD];
-    if (threadIdx.x == 1000) lds_pad[blockIdx.x % MPCG_LDS_PAD] = 0;
-#endif
     if (sol >= batch) return;
     // the lane exchanges assume one wavefront per workgroup (wave_sync): any other launch
     // shape reports an invalid exit code instead of racing
@@ -120,9 +78,7 @@
     // slot is the workgroup's: one solve at a time runs on a workgroup and rewrites its slot before reading
     // it (the blocks per linearisation, the refinement scratch per refinement), so a work-queue launch
     // needs grid slots, not batch (mpcg_instance.h launch_instance)
-    // (the split launch: the solve's, whose blocks and carry outlive the launch)
-    constexpr bool SPLIT = MODE != MODE_FUSED;
-    double* const gsol = gws + (size_t)(SPLIT ? sol : (int)blockIdx.x) * ws_doubles<C>();  // this workgroup's workspace
+    double* const gsol = gws + (size_t)(int)blockIdx.x * ws_doubles<C>();  // this workgroup's workspace
     double* const gF = GFH ? gsol : nullptr;
     // the iterative refinement's scratch (rare path): unrefined step, its multipliers, dynamics rhs
     double* const g_ddz0 = gsol + gfh_doubles<C>();
@@ -140,28 +96,6 @@
         else return S.H[kq];
     };
     STAMP_DECL
-    // the split launch's carry block (Carry<C>): a solve that has ended skips the later launches
-    using CB = Carry<C>;
-    double* const gcar = g_ddz0 + itref_doubles<C>();
-    const bool from_carry = SPLIT && (MODE == MODE_QP || split_it > 0);
-    if (from_carry && gcar[CB::META + 1] != 0.0) return;
-    auto carry_cp = [&](size_t off, double* a, int n, bool store) {
-        for (int e = lane; e < n; e += 64) {
-            if (store) gcar[off + e] = a[e];
-            else a[e] = gcar[off + e];
-        }
-    };
-    auto carry_lin = [&](bool store) {
-        carry_cp(CB::G, &S.g[0][0], (int)(sizeof(S.g) / 8), store);
-        carry_cp(CB::B, &S.b[0][0], (int)(sizeof(S.b) / 8), store);
-        carry_cp(CB::DG, &S.Dg[0][0], (int)(sizeof(S.Dg) / 8), store);
-        carry_cp(CB::HD, &S.hd[0][0], (int)(sizeof(S.hd) / 8), store);
-        carry_cp(CB::DISC, &S.disc[0][0], (int)(sizeof(S.disc) / 8), store);
-        if constexpr (!GFH) {
-            carry_cp(CB::H, &S.H[0][0], (int)(sizeof(S.H) / 8), store);
-            carry_cp(CB::F, &S.F[0][0][0], (int)(sizeof(S.F) / 8), store);
-        }
-    };
 
     // NLP multipliers carried over from the previous solve of this planner
     // (zero for a fresh or reset acados capsule)
@@ -170,19 +104,15 @@
     LaneRows<C> LR;
     LR.k = k;
     LR.part = part;
-    if constexpr (C::BOUNDS_SEL) {
-        LR.prb = &pr;
-    } else {
 #pragma unroll
-        for (int j = 0; j < BVS; ++j) {
-            const int v = LR.var(j);
-            double lo = 0.0, hi = 0.0;
+    for (int j = 0; j < BVS; ++j) {
+        const int v = LR.var(j);
+        double lo = 0.0, hi = 0.0;
 #pragma unroll
-            for (int i = 0; i < NZ; ++i)
-                if (v == i) { lo = i < NU ? pr.lbu[i] : pr.lbx[i - NU]; hi = i < NU ? pr.ubu[i] : pr.ubx[i - NU]; }
-            LR.lo[j] = lo;
-            LR.hi[j] = hi;
-        }
+        for (int i = 0; i < NZ; ++i)
+            if (v == i) { lo = i < NU ? pr.lbu[i] : pr.lbx[i - NU]; hi = i < NU ? pr.ubu[i] : pr.ubx[i - NU]; }
+        LR.lo[j] = lo;
+        LR.hi[j] = hi;
     }
     // gradient (x, y, psi) and gap of h row hh of this lane's stage
     auto rowg = [&](int hh, double& a, double& b, double& c) {
@@ -265,20 +195,13 @@
     Rows<C> R;
 #pragma unroll
     for (int r = 0; r < HS; ++r)
-        R.nlam[r] = from_carry ? gcar[CB::NLAM + 64 * r + lane]
-                               : (lam_in && LR.h_on(r)) ? lam_in[(size_t)k * LAMS + NX + LR.hrow(r)] : 0.0;
+        R.nlam[r] = (lam_in && LR.h_on(r)) ? lam_in[(size_t)k * LAMS + NX + LR.hrow(r)] : 0.0;
 
     // ---- load warm start (loadWarmstart, acados_solver_interface.cpp:274-284)
-    if (from_carry) {
-        // (the split launch: the iterate the previous launch of this solve left)
-        carry_cp(CB::Z, &S.z[0][0], (N + 1) * NZ, false);
-        carry_cp(CB::PI, &S.pi_nlp[0][0], N * NX, false);
-    } else {
-        const double* w = io.warm + (size_t)sol * (N + 1) * NZ;
-        for (int e = lane; e < (N + 1) * NZ; e += 64) (&S.z[0][0])[e] = w[e];
-        for (int e = lane; e < N * NX; e += 64)
-            (&S.pi_nlp[0][0])[e] = lam_in ? lam_in[(size_t)(e / NX) * LAMS + e % NX] : 0.0;
-    }
+    const double* w = io.warm + (size_t)sol * (N + 1) * NZ;
+    for (int e = lane; e < (N + 1) * NZ; e += 64) (&S.z[0][0])[e] = w[e];
+    for (int e = lane; e < N * NX; e += 64)
+        (&S.pi_nlp[0][0])[e] = lam_in ? lam_in[(size_t)(e / NX) * LAMS + e % NX] : 0.0;
     if (lane < NX) S.xinit[lane] = io.xinit[(size_t)sol * NX + lane];
     for (int e = lane; e <= N; e += 64) S.dH[e][C::NDH - 1] = 0.0;
     // the capsule's QP memory, if any: the previous QP's solution, whose row multipliers are
@@ -320,34 +243,19 @@
     // non-finite mu ends the QP with the NaN status) and t / lambda floor (DESIGN.md §2.2), read once
     const double mu_max = PH ? __builtin_inf() : pr.qp_mu_max > 0.0 ? pr.qp_mu_max : __builtin_inf(), tmin = pr.qp_t_min;
     // HPIPM's iterative refinement of the corrector direction (qp_itref_corr_max, DESIGN.md §2.2)
-    const bool itref_on = MPCG_ITREF && p_itref > 0;
+    const bool itref_on = p_itref > 0;
     int acados_status = AC_SUCCESS, qp_status = AC_SUCCESS, sqp_iter = 0, qp_total = 0, n_maxit = 0;
     double res_eq = 0.0;
     double nlp_stat = 0.0, nlp_ineq = 0.0, nlp_comp = 0.0;  // NLP residuals of the last linearisation
     bool nlp_nonfinite = false;
-    if (from_carry) {
-        res_eq = gcar[CB::META + 0];
-        acados_status = (int)gcar[CB::META + 2];
-        qp_status = (int)gcar[CB::META + 3];
-        sqp_iter = (int)gcar[CB::META + 4];
-        qp_total = (int)gcar[CB::META + 5];
-        n_maxit = (int)gcar[CB::META + 6];
-    }
-    // the split launch: the interior-point launch's solve ends at a failed QP (the loop's breaks) or
-    // after the last RTI iteration
-    bool ended = true;
 
-    for (int it = SPLIT ? split_it : 0; sqp_mode || it < pr.sqp_iters; ++it) {
+    for (int it = 0; sqp_mode || it < pr.sqp_iters; ++it) {
         // parameter loads are re-issued where they are used rather than hoisted out of
         // the SQP / QP loops into registers that stay live (and spill) across them
         if constexpr (C::RELOAD_PARAMS) asm volatile("" : "+v"(pk));
         // =============== preparation: linearise every stage ===============
         STAMP_BEGIN();
-        if constexpr (MODE == MODE_QP) {
-            // the split launch: the linearisation launch's blocks (GFH: already in the solve's workspace)
-            carry_lin(false);
-            if (lane < NX) S.dz[0][NU + lane] = S.xinit[lane] - S.z[0][NU + lane];
-        } else {
+        {
             double zk[NZ];
 #pragma unroll
             for (int i = 0; i < NZ; ++i) zk[i] = S.z[ks][i];
@@ -367,16 +275,6 @@
                 for (int i = 0; i < 6; ++i) hb6[i] = acc[i];
             }
             double resl = 0.0;
-            // MSPLIT: the MIRROR sweeps run on all parts of a stage, each accumulating its rows of the
-            // eigenvectors (mirror_rows); the stage matrix goes out from part 0 and the other parts'
-            // rows come back through MX, a per-stage exchange area over the Riccati arrays P, Lc, Y
-            // and the box sums (all dead during the linearisation)
-            constexpr int MNA = NZ == 8 ? NZ - 1 : NZ;  // the slack model's decoupled slack diagonal aside
-            constexpr int MRV = (MNA + PARTS - 1) / PARTS;
-            constexpr int MXS = imax(MNA * (MNA + 1) / 2, (MNA - (MNA + PARTS - 1) / PARTS) * MNA) + 1;
-            double* const MX = &S.P[0][0];
-            static_assert(!MSPLIT || offsetof(LdsOf<C>, Dg) - offsetof(LdsOf<C>, P) >= sizeof(double) * N * MXS,
-                          "MIRROR exchange area (P, Lc, Y, bx)");
             double H[NZ][NZ];
             if (stage_lane && k < N) {
                 double g[NZ], xn[NX], pi[NX];
@@ -426,19 +324,7 @@
                 H[X1][X1] += hb6[3]; H[X1][X2] += hb6[4]; H[X2][X1] += hb6[4];
                 H[X2][X2] += hb6[5];
                 STAMP_LAP(13);
-                if constexpr (MSPLIT) {
-                    // mirror()'s symmetrisation, then the upper triangle (and the slack diagonal's
-                    // square, which enters the sweeps' convergence test) to the stage's exchange slot
-#pragma unroll
-                    for (int i = 0; i < MNA; ++i)
-#pragma unroll
-                        for (int j = i + 1; j < MNA; ++j) H[i][j] = 0.5 * (H[i][j] + H[j][i]);
-#pragma unroll
-                    for (int i = 0; i < MNA; ++i)
-#pragma unroll
-                        for (int j = i; j < MNA; ++j) MX[k * MXS + sym(j, i)] = H[i][j];
-                    MX[k * MXS + MXS - 1] = NZ == 8 ? H[NZ - 1][NZ - 1] * H[NZ - 1][NZ - 1] : 0.0;
-                } else if constexpr (C::MODEL == 0 && NZ == 8) {
+                if constexpr (C::MODEL == 0 && NZ == 8) {
                     // the slack row/column of the slack model is exactly zero off the
                     // diagonal (quadratic slack cost, linear in every h row, no dynamics
                     // coupling): MIRROR of the 8x8 block = MIRROR of the leading 7x7 block
@@ -475,8 +361,7 @@
                     mirror<NZ>(H, pr.reg_eps);
                 }
                 STAMP_LAP(14);
-                if constexpr (MSPLIT) {
-                } else if constexpr (C::COMPACT) {
+                if constexpr (C::COMPACT) {
 #pragma unroll
                     for (int i = 0; i < NZ; ++i)
 #pragma unroll
@@ -500,56 +385,6 @@
                     else Hb(N)[sym(i, i)] = pr.reg_eps;
                 }
             }
-            if constexpr (MSPLIT) {
-                wave_sync();
-                if (k < N) {
-                    double dx2 = 0.0;
-                    if (part != 0) {
-#pragma unroll
-                        for (int i = 0; i < MNA; ++i)
-#pragma unroll
-                            for (int j = i; j < MNA; ++j) H[i][j] = MX[k * MXS + sym(j, i)];
-                    }
-                    dx2 = MX[k * MXS + MXS - 1];
-                    double Vr[MRV][MNA];
-                    mirror_rows<NZ, MNA, PARTS>(H, Vr, part, dx2);
-                    wave_sync();  // every part has read the stage matrix
-                    if (part != 0) {
-#pragma unroll
-                        for (int t = 0; t < MRV; ++t) {
-                            const int r = part + PARTS * t;
-                            if (r >= MNA) continue;
-                            const int sl = r - 1 - (r - 1) / PARTS;  // rank among the rows of parts 1..
-#pragma unroll
-                            for (int j = 0; j < MNA; ++j) MX[k * MXS + sl * MNA + j] = Vr[t][j];
-                        }
-                    }
-                    wave_sync();
-                    if (part == 0) {
-                        double V[MNA][MNA];
-#pragma unroll
-                        for (int r = 0; r < MNA; ++r) {
-                            if (r % PARTS == 0) {
-#pragma unroll
-                                for (int j = 0; j < MNA; ++j) V[r][j] = Vr[r / PARTS][j];
-                            } else {
-                                const int sl = r - 1 - (r - 1) / PARTS;
-#pragma unroll
-                                for (int j = 0; j < MNA; ++j) V[r][j] = MX[k * MXS + sl * MNA + j];
-                            }
-                        }
-                        mirror_rebuild<NZ, MNA>(H, V, pr.reg_eps);
-                        if constexpr (NZ == 8) {
-                            const double hs = H[NZ - 1][NZ - 1];
-                            H[NZ - 1][NZ - 1] = (hs >= -pr.reg_eps && hs <= pr.reg_eps) ? pr.reg_eps : fabs(hs);
-                        }
-#pragma unroll
-                        for (int i = 0; i < NZ; ++i)
-#pragma unroll
-                            for (int j = 0; j <= i; ++j) Hb(k)[sym(i, j)] = H[i][j];
-                    }
-                }
-            }
             res_eq = wave_max(resl);
             if (lane < NX) S.dz[0][NU + lane] = S.xinit[lane] - S.z[0][NU + lane];
         }
@@ -557,19 +392,6 @@
         if constexpr (GFH) __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
         wave_sync();
         STAMP_END(0);
-        if constexpr (MODE == MODE_LIN) {
-            // the split launch ends here: the linearisation (and, first, the iterate and counters) to the carry
-            carry_lin(true);
-            if (split_it == 0) {
-                carry_cp(CB::Z, &S.z[0][0], (N + 1) * NZ, true);
-                carry_cp(CB::PI, &S.pi_nlp[0][0], N * NX, true);
-#pragma unroll
-                for (int r = 0; r < HS; ++r) gcar[CB::NLAM + 64 * r + lane] = R.nlam[r];
-                if (lane >= 1 && lane < 8) gcar[CB::META + lane] = 0.0;
-            }
-            if (lane == 0) gcar[CB::META + 0] = res_eq;
-            return;
-        }
 
         // =============== feedback: QP by Riccati interior point ===============
         STAMP_BEGIN();
@@ -706,7 +528,7 @@
         }
         {
             const double thr0 = pr.qp_thr0, mu0 = pr.qp_mu0;
-            const bool mv = MPCG_MOVE && p_move;
+            const bool mv = p_move;
             auto cold = [&](int s, double gap) {
                 const double t0 = gap > thr0 ? gap : thr0;
                 R.t[s] = t0;
@@ -772,7 +594,7 @@
                 for (int i = 0; i < NB; ++i) rh[i] = qh[i] = 0.0;
 #pragma unroll
                 for (int i = 0; i < NBT; ++i) dbh[i] = 0.0;
-                // FUSE_BAR: the predictor's barrier terms (rc = l t, the same operations as the
+                // the predictor's barrier terms (rc = l t, the same operations as the
                 // barrier pass) from the row state just computed
                 auto bar0 = [&](int s, double& coef, double& wgt) {
                     const double l = R.l[s], t = R.t[s], itt = R.it(s);
@@ -801,24 +623,22 @@
                         rb = R.l[2 * j + 1] - R.l[2 * j];
                         row_res(2 * j, -dzv, zv - LR.lo_at(j));
                         row_res(2 * j + 1, dzv, LR.hi_at(j) - zv);
-                        if constexpr (FUSE_BAR) {
-                            double c0, w0, c1, w1;
-                            bar0(2 * j, c0, w0);
-                            bar0(2 * j + 1, c1, w1);
-                            qb = c1 - c0;
-                            dd = w0 + w1;
-                        }
+                        double c0, w0, c1, w1;
+                        bar0(2 * j, c0, w0);
+                        bar0(2 * j + 1, c1, w1);
+                        qb = c1 - c0;
+                        dd = w0 + w1;
                     } else {
                         R.rin[2 * j] = R.rin[2 * j + 1] = 0.0;
                         R.set_it(2 * j, 1.0);
                         R.set_it(2 * j + 1, 1.0);
                     }
                     if (k <= N && LR.var(j) < NZ) {
-                        if constexpr (!RES_SPLIT) S.bx[k][LR.var(j)] = rb;
-                        if constexpr (FUSE_BAR) {
-                            if constexpr (!RES_SPLIT) S.q[k][LR.var(j)] = qb;  // dead since the last vector pass
-                            S.dH[k][LR.var(j)] = dd;
+                        if constexpr (!RES_SPLIT) {
+                            S.bx[k][LR.var(j)] = rb;
+                            S.q[k][LR.var(j)] = qb;  // dead since the last vector pass
                         }
+                        S.dH[k][LR.var(j)] = dd;
                     }
                 }
 #pragma unroll
@@ -844,19 +664,17 @@
                     rh[0] += a * l; rh[1] += bq * l; rh[2] += c * l;
                     if constexpr (NB == 4) rh[3] += C::slack_coef(hh) * l;
                     row_res(HB + r, dd, gap);
-                    if constexpr (FUSE_BAR) {
-                        double coef, wgt;
-                        bar0(HB + r, coef, wgt);
-                        double dg[NB];
-                        dg[0] = a; dg[1] = bq; dg[2] = c;
-                        if constexpr (NB == 4) dg[3] = C::slack_coef(hh);
+                    double coef, wgt;
+                    bar0(HB + r, coef, wgt);
+                    double dg[NB];
+                    dg[0] = a; dg[1] = bq; dg[2] = c;
+                    if constexpr (NB == 4) dg[3] = C::slack_coef(hh);
 #pragma unroll
-                        for (int i = 0; i < NB; ++i) qh[i] += dg[i] * coef;
+                    for (int i = 0; i < NB; ++i) qh[i] += dg[i] * coef;
 #pragma unroll
-                        for (int cc = 0; cc < NB; ++cc)
+                    for (int cc = 0; cc < NB; ++cc)
 #pragma unroll
-                            for (int aa = cc; aa < NB; ++aa) dbh[cpk(NB, aa, cc)] += dg[aa] * wgt * dg[cc];
-                    }
+                        for (int aa = cc; aa < NB; ++aa) dbh[cpk(NB, aa, cc)] += dg[aa] * wgt * dg[cc];
                 }
                 double acc[NB], aq[NB], ab[NBT];
 #pragma unroll
@@ -867,12 +685,10 @@
                 for (int p = 1; p < PARTS; ++p) {
 #pragma unroll
                     for (int i = 0; i < NB; ++i) acc[i] += lane_down(rh[i], p);
-                    if constexpr (FUSE_BAR) {
 #pragma unroll
-                        for (int i = 0; i < NB; ++i) aq[i] += lane_down(qh[i], p);
+                    for (int i = 0; i < NB; ++i) aq[i] += lane_down(qh[i], p);
 #pragma unroll
-                        for (int i = 0; i < NBT; ++i) ab[i] += lane_down(dbh[i], p);
-                    }
+                    for (int i = 0; i < NBT; ++i) ab[i] += lane_down(dbh[i], p);
                 }
                 if constexpr (RES_SPLIT) {
                     // part 0's stage sums of the h rows to the owners of the block variables
@@ -970,18 +786,16 @@
                         double a = 0.0;
 #pragma unroll
                         for (int j = 0; j < NZ; ++j) a += Hat(k, i, j) * dzk[j];
-                        if constexpr (!RES_SPLIT) Hdz[i] = a;
+                        Hdz[i] = a;
                         r[i] = a + S.g[k][i] + rbox[i];
                     }
-                    if constexpr (FUSE_BAR) {
-                        // the predictor's Newton gradient and h-row barrier block (barrier pass)
+                    // the predictor's Newton gradient and h-row barrier block (barrier pass)
 #pragma unroll
-                        for (int i = 0; i < NZ; ++i) S.q[k][i] = Hdz[RES_SPLIT ? 0 : i] + S.g[k][i] + S.q[k][i];
+                    for (int i = 0; i < NZ; ++i) S.q[k][i] = Hdz[i] + S.g[k][i] + S.q[k][i];
 #pragma unroll
-                        for (int i = 0; i < NB; ++i) S.q[k][C::bvar(i)] += aq[i];
+                    for (int i = 0; i < NB; ++i) S.q[k][C::bvar(i)] += aq[i];
 #pragma unroll
-                        for (int i = 0; i < NBT; ++i) S.dH[k][NZ + i] = ab[i];
-                    }
+                    for (int i = 0; i < NBT; ++i) S.dH[k][NZ + i] = ab[i];
                     if (k < N) {
 #pragma unroll
                         for (int m = 0; m < NX; ++m) {
@@ -1057,9 +871,12 @@
             bool refining = false;
             int nref = 0;
             for (int phase = 0; phase < 2; ++phase) {
-                // ---- barrier terms + Newton gradient (FUSE_BAR: the predictor's came with the residuals)
+                // ---- barrier terms + Newton gradient (the predictor's came with the residuals, so this pass
+                // runs for the corrector only.  Its arms on `phase == 0` never execute; they stay because
+                // the compiler does not fold them and its allocation of every instance depends on them:
+                // a build without them differed in registers and instruction counts in all four families)
                 STAMP_BEGIN();
-                if ((!FUSE_BAR || phase == 1) && !refining) {
+                if (phase == 1 && !refining) {
                     double qh[NB], dbh[NBT];
 #pragma unroll
                     for (int i = 0; i < NB; ++i) qh[i] = 0.0;
@@ -1144,7 +961,7 @@
                     wave_sync();  // the owner lanes' box sums S.bx
                     if (stage_lane) {
 #pragma unroll
-                        for (int i = 0; i < NZ; ++i) S.q[k][i] = Hdz[RES_SPLIT ? 0 : i] + S.g[k][i] + S.bx[k][i];
+                        for (int i = 0; i < NZ; ++i) S.q[k][i] = Hdz[i] + S.g[k][i] + S.bx[k][i];
 #pragma unroll
                         for (int i = 0; i < NB; ++i) S.q[k][C::bvar(i)] += aq[i];
                         if (phase == 0) {
@@ -1161,37 +978,10 @@
                 if (phase == 0) {
                     constexpr int NT = C::NTRI, NP = C::NPT, DZ = C::NDH - 1;
                     constexpr bool FAC_FLAT = C::FAC_FLAT;
-                    // FAC_PAIR: two lanes per block entry (lanes 2e, 2e + 1 of entry e), each forming the
-                    // cost-to-go product P F[:, ej] on half of the rows (0-2 / 3-4) and its part of
-                    // F[:, ei]' (P F[:, ej]); a DPP add joins the halves.  18 fp64 FMAs per lane and step
-                    // instead of 30 (the nz 7 unicycle: 28 entries, 56 lanes)
-#ifndef MPCG_FAC_PAIR
-#define MPCG_FAC_PAIR 0
-#endif
-                    constexpr bool PAIR_EL = MPCG_FAC_PAIR && FAC_FLAT && NU == 2 && NX == 5 && !C::COMPACT &&
-                                             !C::FCONST && !GFH && 2 * NT <= 64;
-                    // FAC_PF: P_{k+1} F_k formed once per stage -- lane (a, c) < NX x NZ the entry (a, c), 5 FMAs --
-                    // into the box-sum rows (dead from the barrier pass to the vector chains), then every element
-                    // lane F[:, ei]' (P F)[:, ej] from that column: 10 fp64 FMAs per lane and stage instead of 30,
-                    // for one more LDS exchange on the recursion's path (VERDICT r04 item 3; MPCG_FAC_PF=1, A/B)
-#ifndef MPCG_FAC_PF
-#define MPCG_FAC_PF 0
-#endif
-                    constexpr bool FPF = MPCG_FAC_PF && FAC_FLAT && !PAIR_EL && NU == 2 && !C::COMPACT && !C::FCONST &&
-                                         !GFH && NX * NZ <= 64;
-                    const int pa = FPF && lane < NX * NZ ? lane / NZ : 0;  // the lane's entry of P F
-                    const int pcol = FPF && lane < NX * NZ ? lane - pa * NZ : 0;
-                    double* const PFs = &S.bx[0][0];
-                    constexpr int RH = PAIR_EL ? 3 : NX;  // cost-to-go rows per lane
-                    const int el = PAIR_EL ? (lane >> 1) : lane;  // the lane's block entry
-                    const int half = PAIR_EL ? (lane & 1) : 0;
-                    // the lane's rows of P F (half 1: rows 3, 4 and a dummy row 4 with a zero weight)
-                    auto prow = [&](int t) -> int { return PAIR_EL ? (half == 0 ? t : (t < 2 ? 3 + t : 4)) : t; };
-                    auto prow_on = [&](int t) -> bool { return !PAIR_EL || half == 0 || t < 2; };
                     // element lane -> (ei, ej), ei >= ej, of the nz x nz block
                     int ei = 0;
-                    while ((ei + 1) * (ei + 2) / 2 <= el && ei < NZ - 1) ++ei;
-                    const int ej = el < NT ? el - ei * (ei + 1) / 2 : 0;
+                    while ((ei + 1) * (ei + 2) / 2 <= lane && ei < NZ - 1) ++ei;
+                    const int ej = lane < NT ? lane - ei * (ei + 1) / 2 : 0;
                     // barrier entries of (ei, ej); DZ is the always-zero slot
                     const int dhd = (ei == ej) ? ei : DZ;
                     int dhb = DZ;
@@ -1214,12 +1004,12 @@
                     if (!FAC_FLAT && !p_pzero && lane == 0) S.flag = 0;
                     wave_sync();
                     // prefetch of stage N-1's block
-                    const int le = el < NT ? el : 0;
+                    const int le = lane < NT ? lane : 0;
                     double fi[NX], fj[NX], hv;
 #pragma unroll
-                    for (int m = 0; m < NX; ++m) fj[m] = Fat(N - 1, m, FPF ? pcol : ej);
+                    for (int m = 0; m < NX; ++m) fj[m] = Fat(N - 1, m, ej);
 #pragma unroll
-                    for (int t = 0; t < RH; ++t) fi[t] = prow_on(t) ? Fat(N - 1, prow(t), ei) : 0.0;
+                    for (int m = 0; m < NX; ++m) fi[m] = Fat(N - 1, m, ei);
                     // rows of [B A] that vary over the stages: with the constant rows (FCONST) only x+ and
                     // y+; the others stay in fi / fj from the fill above (their per-stage re-evaluation
                     // on the lane's runtime column compiled to branches inside the recursion)
@@ -1240,11 +1030,7 @@
                     };
                     // measured: C4 53.40 -> 52.82 ms with the staging copy, C3 21.01 -> 21.67 (its
                     // compact blocks are rebuilt entry by entry and the copy adds live state): C4 only
-#ifdef MPCG_NO_STAGE
-                    constexpr bool STG = false;  // A/B: the Riccati step reads the global blocks directly
-#else
                     constexpr bool STG = GFH && !C::COMPACT;
-#endif
                     constexpr int NFB = C::NFR * C::NFC;
                     static_assert(!GFH || (NFB <= 64 && C::NHP <= 64), "one staged entry per lane");
                     double gsf = 0.0, gsh = 0.0;  // the staged entries of the next block in flight
@@ -1256,19 +1042,11 @@
                     };
                     if (N >= 2) stage_load(N - 2);
                     hv = Hel(N - 1) + S.dH[N - 1][dhd] + S.dH[N - 1][dhb];
-                    MPCG_UNROLL_FAC
+#pragma unroll
                     for (int kk = N - 1; kk >= 0; --kk) {
                         double Pm[NP];
-                        if constexpr (PAIR_EL) {
-                            // the lane's rows of the cost-to-go (two distinct addresses per read)
 #pragma unroll
-                            for (int t = 0; t < RH; ++t)
-#pragma unroll
-                                for (int l = 0; l < NX; ++l) Pm[t * NX + l] = S.P[kk + 1][sym(prow(t), l)];
-                        } else {
-#pragma unroll
-                            for (int e = 0; e < NP; ++e) Pm[e] = S.P[kk + 1][e];
-                        }
+                        for (int e = 0; e < NP; ++e) Pm[e] = S.P[kk + 1][e];
                         // prefetch of the next (lower) stage's block; it lands while this one is
                         // reduced.  FAC_FLAT: every lane runs one branch-free block, the five row
                         // products advance together, and the prefetch is issued after the pivot
@@ -1289,47 +1067,16 @@
                                 for (int m = 0; m < NFV; ++m)
                                     if (varies(m)) { fi2[m] = FatB(S.Fst, m, ei); fj2[m] = FatB(S.Fst, m, ej); }
                                 hv2 = HelS() + S.dH[kn][dhd] + S.dH[kn][dhb];
-                            } else if constexpr (PAIR_EL) {
-#pragma unroll
-                                for (int m = 0; m < NX; ++m) fj2[m] = Fat(kn, m, ej);
-#pragma unroll
-                                for (int t = 0; t < RH; ++t) fi2[t] = prow_on(t) ? Fat(kn, prow(t), ei) : 0.0;
-                                hv2 = Hel(kn) + S.dH[kn][dhd] + S.dH[kn][dhb];
                             } else {
 #pragma unroll
                                 for (int m = 0; m < NFV; ++m)
-                                    if (varies(m)) { fi2[m] = Fat(kn, m, ei); fj2[m] = Fat(kn, m, FPF ? pcol : ej); }
+                                    if (varies(m)) { fi2[m] = Fat(kn, m, ei); fj2[m] = Fat(kn, m, ej); }
                                 hv2 = Hel(kn) + S.dH[kn][dhd] + S.dH[kn][dhb];
                             }
                         };
                         if constexpr (!FAC_FLAT) prefetch();
                         double v = hv;
-                        if constexpr (PAIR_EL) {
-                            // the lane's rows t of P F[:, ej], then its part of F[:, ei]' (P F[:, ej]) (half 1
-                            // starts from 0), the halves joined on the even lane (DPP row_shl:1)
-                            double tm[RH];
-#pragma unroll
-                            for (int t = 0; t < RH; ++t) tm[t] = 0.0;
-#pragma unroll
-                            for (int l = 0; l < NX; ++l)
-#pragma unroll
-                                for (int t = 0; t < RH; ++t) tm[t] += Pm[t * NX + l] * fj[l];
-                            v = half == 0 ? hv : 0.0;
-#pragma unroll
-                            for (int t = 0; t < RH; ++t) v += fi[t] * tm[t];
-                            v += dpp_d<0x101>(v);
-                            S.Msc[(el < NT && half == 0) ? el : 64 + lane] = v;
-                        } else if constexpr (FPF) {
-                            // (P F)[pa][pcol] = sum_l P[pa][l] F[l][pcol]; fj holds the lane's column pcol
-                            double pf = 0.0;
-#pragma unroll
-                            for (int l = 0; l < NX; ++l) pf += S.P[kk + 1][sym(pa, l)] * fj[l];
-                            PFs[lane < NX * NZ ? lane : NX * NZ + (lane & 7)] = pf;
-                            wave_sync();
-#pragma unroll
-                            for (int m = 0; m < NX; ++m) v += fi[m] * PFs[m * NZ + ej];
-                            S.Msc[lane < NT ? lane : 64 + lane] = v;
-                        } else if constexpr (FAC_FLAT) {
+                        if constexpr (FAC_FLAT) {
                             double tm[NX];
 #pragma unroll
                             for (int m = 0; m < NX; ++m) tm[m] = 0.0;
@@ -1357,10 +1104,9 @@
                           if (FAC_FLAT || lane < NP) {
                             // the pivot block (element lanes 0, 1, 2) straight from their registers:
                             // the recursion's critical path skips one LDS round trip
-                            constexpr int LS_ = PAIR_EL ? 2 : 1;  // lane stride of the block entries
                             const double m00 = FAC_FLAT ? readlane_d(v, 0) : S.Msc[0];
-                            const double m10 = FAC_FLAT ? readlane_d(v, LS_) : S.Msc[1];
-                            const double m11 = FAC_FLAT ? readlane_d(v, 2 * LS_) : S.Msc[2];
+                            const double m10 = FAC_FLAT ? readlane_d(v, 1) : S.Msc[1];
+                            const double m11 = FAC_FLAT ? readlane_d(v, 2) : S.Msc[2];
                             const double mi0 = S.Msc[sym(NU + pi_, 0)], mi1 = S.Msc[sym(NU + pi_, 1)];
                             const double mj0 = S.Msc[sym(NU + pj_, 0)], mj1 = S.Msc[sym(NU + pj_, 1)];
                             const double mij = S.Msc[sym(NU + pi_, NU + pj_)];
@@ -1649,7 +1395,7 @@
                     double pu[NX];
 #pragma unroll
                     for (int i = 0; i < NX; ++i) pu[i] = S.q[N][NU + i];
-                    MPCG_UNROLL_CHAIN
+#pragma unroll
                     for (int kk = PAIR ? N - 2 : N - 1; kk >= 1; kk -= PAIR ? 2 : 1) {  // p_0 is not needed
                         double pn[RS];
 #pragma unroll
@@ -1659,7 +1405,6 @@
                         if constexpr (C::REC_FLAT) {
                             // branch-free record: lanes that do not own the step write to the
                             // dead pivot scratch (the stores then sink below the broadcast)
-#ifndef MPCG_REC_SELECT
                             // owner lanes of step kk: the literal mask of stage kk's parts; both
                             // candidate addresses are lane constants offset by the step's stride
                             const unsigned long long OWN = ((1ull << PARTS) - 1) << (kk * PARTS);
@@ -1671,11 +1416,6 @@
                                 const unsigned on = rv[t] ? lds_addr(&pch[rs[t]]) : off;
                                 lds_store(sel_lanes(OWN, off, on) + kk * NX * 8, pn[t]);
                             }
-#else
-#pragma unroll
-                            for (int t = 0; t < RS; ++t)
-                                *((k == kk && rv[t]) ? &pch[kk * NX + rs[t]] : &S.Msc[64 * (t & 1) + lane]) = pn[t];
-#endif
                         } else if (k == kk) {
 #pragma unroll
                             for (int t = 0; t < RS; ++t)
@@ -1747,7 +1487,7 @@
                     double dxu[NX];
 #pragma unroll
                     for (int i = 0; i < NX; ++i) dxu[i] = 0.0;
-                    MPCG_UNROLL_CHAIN
+#pragma unroll
                     for (int kk = PAIR ? 1 : 0; kk < N; kk += PAIR ? 2 : 1) {
                         double dn[RS];
 #pragma unroll
@@ -1755,7 +1495,6 @@
                             dn[t] = chain_dot<NX>(ec[t], Gc[t], dxu);
                         }
                         if constexpr (C::REC_FLAT) {
-#ifndef MPCG_REC_SELECT
                             // dummies in the box-sum rows (the backward chain's values are read)
                             const unsigned long long OWN = ((1ull << PARTS) - 1) << (kk * PARTS);
                             static_assert((N - 1) * NZ + 8 <= (N + 1) * NZ, "record dummies inside the box-sum rows");
@@ -1765,11 +1504,6 @@
                                 const unsigned on = rv[t] ? lds_addr(&S.ddz[1][NU + rs[t]]) : off;
                                 lds_store(sel_lanes(OWN, off, on) + kk * NZ * 8, dn[t]);
                             }
-#else
-#pragma unroll
-                            for (int t = 0; t < RS; ++t)
-                                *((k == kk && rv[t]) ? &S.ddz[kk + 1][NU + rs[t]] : &S.Msc[64 * (t & 1) + lane]) = dn[t];
-#endif
                         } else if (k == kk) {
 #pragma unroll
                             for (int t = 0; t < RS; ++t)
@@ -1828,7 +1562,6 @@
 #pragma unroll
                         for (int i = 0; i < NX; ++i) {
                             if (k == 0) S.ddz[0][NU + i] = 0.0;
-                            if constexpr (PIN_SPLIT) continue;
                             double a = pmine[i];
 #pragma unroll
                             for (int j = 0; j < NX; ++j) a += S.P[k + 1][sym(i, j)] * dxn[j];
@@ -1838,23 +1571,6 @@
                         if (k == N - 1) {
 #pragma unroll
                             for (int u = 0; u < NU; ++u) S.ddz[N][u] = 0.0;
-                        }
-                    }
-                    if constexpr (PIN_SPLIT) {
-                        // the new dynamics multipliers, rows split over the parts like the chains' rows
-                        if (k < N) {
-                            double dxn[NX];
-#pragma unroll
-                            for (int i = 0; i < NX; ++i) dxn[i] = S.ddz[k + 1][NU + i];
-#pragma unroll
-                            for (int t = 0; t < RS; ++t) {
-                                if (!rv[t]) continue;
-                                const int i = rs[t];
-                                double a = pmine[i];
-#pragma unroll
-                                for (int j = 0; j < NX; ++j) a += S.P[k + 1][sym(i, j)] * dxn[j];
-                                S.pin[k][i] = a;
-                            }
                         }
                     }
                 } else
@@ -1934,11 +1650,7 @@
                     // predicated store off the VALU path) and read back after the chain.  The
                     // register-starved bicycle instance did the selects into registers until round 4;
                     // the records keep six doubles per chain out of its registers: scratch 560 -> 504
-                    // B/lane, C3 19.50 -> 18.99 ms (profiles/r04i_ab_*; MPCG_C3_CHAIN_REC=0: A/B)
-#ifndef MPCG_C3_CHAIN_REC
-#define MPCG_C3_CHAIN_REC 1
-#endif
-                    constexpr bool CHAIN_REC = !C::COMPACT || MPCG_C3_CHAIN_REC;
+                    // B/lane, C3 19.50 -> 18.99 ms (profiles/r04i_ab_*)
                     double pu[NX], pmine[NX];
                     double* const pch = &S.bx[0][0];
                     static_assert((N + 1) * NZ >= N * NX, "chain storage");
@@ -1954,18 +1666,14 @@
                             for (int j = 0; j < NX; ++j) a += G[i][j] * pu[j];
                             pn[i] = a;
                         }
-                        if (CHAIN_REC && lane == kk * PARTS) {
+                        if (lane == kk * PARTS) {
 #pragma unroll
                             for (int i = 0; i < NX; ++i) pch[kk * NX + i] = pn[i];
                         }
-                        const bool mine = !CHAIN_REC && (k == kk - 1) && (part == 0);
 #pragma unroll
-                        for (int i = 0; i < NX; ++i) {
-                            pu[i] = readlane_d(pn[i], kk * PARTS);
-                            if constexpr (!CHAIN_REC) pmine[i] = mine ? pu[i] : pmine[i];
-                        }
+                        for (int i = 0; i < NX; ++i) pu[i] = readlane_d(pn[i], kk * PARTS);
                     }
-                    if constexpr (CHAIN_REC) {
+                    {
                         wave_sync();
                         const double* src = (kq + 1 < N) ? pch + (kq + 1) * NX : &S.q[N][NU];
 #pragma unroll
@@ -2015,22 +1723,16 @@
                             for (int j = 0; j < NX; ++j) a += G[j][i] * dxu[j];
                             dn[i] = a;
                         }
-                        if (CHAIN_REC && lane == kk * PARTS) {
+                        if (lane == kk * PARTS) {
 #pragma unroll
                             for (int i = 0; i < NX; ++i) S.ddz[kk + 1][NU + i] = dn[i];
                         }
-                        const bool mine = !CHAIN_REC && (k == kk + 1) && (part == 0);
 #pragma unroll
-                        for (int i = 0; i < NX; ++i) {
-                            dxu[i] = readlane_d(dn[i], kk * PARTS);
-                            if constexpr (!CHAIN_REC) dxmine[i] = mine ? dxu[i] : dxmine[i];
-                        }
+                        for (int i = 0; i < NX; ++i) dxu[i] = readlane_d(dn[i], kk * PARTS);
                     }
-                    if constexpr (CHAIN_REC) {
-                        wave_sync();
+                    wave_sync();
 #pragma unroll
-                        for (int i = 0; i < NX; ++i) dxmine[i] = (k >= 1 && k < N) ? S.ddz[k][NU + i] : 0.0;
-                    }
+                    for (int i = 0; i < NX; ++i) dxmine[i] = (k >= 1 && k < N) ? S.ddz[k][NU + i] : 0.0;
                     STAMP_LAP(9);
                     if (own) {
                         double du[NU], dxn[NX];
@@ -2060,7 +1762,7 @@
                         for (int u = 0; u < NU; ++u) S.ddz[k][u] = du[u];
 #pragma unroll
                         for (int i = 0; i < NX; ++i) {
-                            if (!CHAIN_REC || k == 0) S.ddz[k][NU + i] = dxmine[i];  // 0 at k = 0
+                            if (k == 0) S.ddz[k][NU + i] = dxmine[i];  // 0 at k = 0
                             double a = pmine[i];
 #pragma unroll
                             for (int j = 0; j < NX; ++j) a += S.P[k + 1][sym(i, j)] * dxn[j];
@@ -2132,19 +1834,16 @@
                         dl = -(rc + l * dt) * R.it(s);
                     };
                     // step to the boundary: min over rows of -t/dt and -l/dl = 1 / max(-dt/t, -dl/l)
-                    // STEP_FORMS: in the predictor rc = l t, so dl = -l (t + dt) / t and a row's
+                    // In the predictor rc = l t, so dl = -l (t + dt) / t and a row's
                     // multiplier blocks (dl < 0) exactly when t + dt > 0, at -dl / l = 1 + dt / t: the row's
                     // bound is max(-dt/t, 1 + dt/t) (the second term is <= 0 < the first when it does not
                     // block), no reciprocal of l and no branch; in the corrector the branch on dl < 0 is a
                     // select (the wave computes the reciprocal whenever any lane needs it)
-#ifndef MPCG_STEP_FORMS
-#define MPCG_STEP_FORMS 1
-#endif
                     double rmax = 0.0;
                     // the corrector's sums for the conditional predictor-corrector: mu_aff of the corrected
                     // direction at step a is (sum l t + a sum (l dt + t dl) + a^2 sum dl dt) / M
                     double cb = 0.0, cq = 0.0;
-                    if (MPCG_STEP_FORMS && ph == 0) {
+                    if (ph == 0) {
 #pragma unroll
                         for (int s = 0; s < C::SLOTS; ++s) {
                             if (!active(s)) continue;
@@ -2159,17 +1858,11 @@
                             if (!active(s)) continue;
                             double dt, dl;
                             row_step(s, dt, dl);
-                            if (MPCG_COND) {
-                                cb += R.l[s] * dt + R.t[s] * dl;
-                                cq += dl * dt;
-                            }
+                            cb += R.l[s] * dt + R.t[s] * dl;
+                            cq += dl * dt;
                             rmax = fmax(rmax, -dt * R.it(s));
-                            if (MPCG_STEP_FORMS) {
-                                const double c = -dl * frcp(R.l[s]);
-                                rmax = fmax(rmax, dl < 0.0 ? c : 0.0);
-                            } else if (dl < 0.0) {
-                                rmax = fmax(rmax, -dl * frcp(R.l[s]));
-                            }
+                            const double c = -dl * frcp(R.l[s]);
+                            rmax = fmax(rmax, dl < 0.0 ? c : 0.0);
                         }
                     }
                     rmax = wave_max(rmax);
@@ -2194,7 +1887,7 @@
                         sig = sig * sig * sig;
                         sigma_mu = sig * mu;
                     } else {
-                        if (MPCG_COND && p_cond && !centred && nref == 0) {
+                        if (p_cond && !centred && nref == 0) {
                             // HPIPM cond_pred_corr: mu_aff of the corrected direction at its boundary step
                             // (the expanded form of sum (l + a dl)(t + a dt), from the step-length loop's sums)
                             const double ac = fmin(amax, 1.0);
@@ -2622,28 +2315,6 @@
         // SQP-RTI: the reference's loop stops after a QP that did not succeed
         // (acados_solver_interface.cpp:105); a full SQP call continues after a max-iter QP
         if (!sqp_mode && qstat != AC_SUCCESS) break;
-        if constexpr (MODE == MODE_QP) {
-            ended = it + 1 >= pr.sqp_iters;
-            break;
-        }
-    }
-    if constexpr (MODE == MODE_QP) {
-        // the split launch: the iterate and counters to the carry; a solve that has ended writes its outputs
-        if (lane == 0) {
-            gcar[CB::META + 1] = ended ? 1.0 : 0.0;
-            gcar[CB::META + 2] = acados_status;
-            gcar[CB::META + 3] = qp_status;
-            gcar[CB::META + 4] = sqp_iter;
-            gcar[CB::META + 5] = qp_total;
-            gcar[CB::META + 6] = n_maxit;
-        }
-        if (!ended) {
-            carry_cp(CB::Z, &S.z[0][0], (N + 1) * NZ, true);
-            carry_cp(CB::PI, &S.pi_nlp[0][0], N * NX, true);
-#pragma unroll
-            for (int r = 0; r < HS; ++r) gcar[CB::NLAM + 64 * r + lane] = R.nlam[r];
-            return;
-        }
     }
 
     // ---- completeOneIteration (acados_solver_interface.cpp:162-204)

@@ -1,7 +1,7 @@
 """A/B timing of kernel variants (compile-time switches of csrc/mpcg_sqp.h).
 
-    python scripts/ab_bench.py --build base: bsel:-DMPCG_BOUNDS_SEL=1      # CPU: build the variants
-    python scripts/ab_bench.py --run base,bsel --configs C2,C3,C4 [--reps 2]  # GPU: bench each
+    python scripts/ab_bench.py --build base: nocarry:-DMPCG_RES_CARRY=0  # CPU: build the variants
+    python scripts/ab_bench.py --run base,nocarry --configs C2,C1 [--reps 2]  # GPU: bench each
 
 Each variant is a full libmpcg.so under build/ab/<name>/ with the given extra flags; the
 GPU side runs bench.py --full (no CPU leg) once per (rep, variant, config), alternating variants,

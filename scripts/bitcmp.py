@@ -2,6 +2,10 @@
 through two or more libmpcg.so builds (MPCG_LIB, one child process each), outputs compared exactly.
 
     python scripts/bitcmp.py --libs prod,build/ab/x/libmpcg.so --configs C2,C4 [--profile hpipm]
+
+A library built for another ABI fails at load.  --accept-older-abi N (off by default) lets the children
+load a library of the older ABI N as well (MPCG_ABI_ACCEPT_OLDER), for a comparison against an earlier
+round's build.
 """
 import argparse
 import json
@@ -33,6 +37,8 @@ def main():
     ap.add_argument("--libs", default="prod")
     ap.add_argument("--configs", default="C2")
     ap.add_argument("--profile", default="hpipm")
+    ap.add_argument("--accept-older-abi", type=int, default=None, metavar="N",
+                    help="let the children load a library of the older ABI N too (default: the current ABI only)")
     ap.add_argument("--child", nargs=3, help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.child:
@@ -42,12 +48,13 @@ def main():
     libs = [os.path.join(ROOT, "oscar_mpc_planner_mr_modification_amd", "libmpcg.so") if x == "prod" else
             os.path.join(ROOT, x) for x in a.libs.split(",")]
     tmp = tempfile.mkdtemp()
+    env_abi = {} if a.accept_older_abi is None else {"MPCG_ABI_ACCEPT_OLDER": str(a.accept_older_abi)}
     for cfg in a.configs.split(","):
         outs = []
         for i, lib in enumerate(libs):
             f = os.path.join(tmp, f"{cfg}_{i}.npz")
             subprocess.run([sys.executable, os.path.abspath(__file__), "--child", cfg, a.profile, f],
-                           env=dict(os.environ, MPCG_LIB=lib, MPCG_ABI_ACCEPT_OLDER="8"), check=True)
+                           env=dict(os.environ, MPCG_LIB=lib, **env_abi), check=True)
             outs.append(np.load(f))
         ref = outs[0]
         for lib, o in zip(libs[1:], outs[1:]):
