@@ -144,6 +144,22 @@ def build_stage_probe(force: bool = False) -> str:
     return so
 
 
+def build_mirror_probe(force: bool = False) -> str:
+    """build/probe/libmirror_probe.so: the test-only translation unit tests/cpp/mirror_probe.hip (one
+    wavefront per workgroup around mirror / mirror_blocks_ok / mirror_stage of mpcg_device.h,
+    tests/test_gpu_mirror_blocks.py), compiled with the flags of the kernel instances."""
+    src = os.path.join(ROOT, "tests", "cpp", "mirror_probe.hip")
+    out_dir = os.path.join(BUILD, "probe")
+    so = os.path.join(out_dir, "libmirror_probe.so")
+    deps = [src, os.path.join(INCLUDE, "mpcg.h"), __file__, os.path.join(CSRC, "mpcg_device.h")]
+    if force or _stale(so, deps):
+        os.makedirs(out_dir, exist_ok=True)
+        obj = _hipcc_obj(src, os.path.join(out_dir, "mirror_probe.o"))
+        subprocess.run(["hipcc", f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", so + ".tmp", obj], check=True)
+        os.replace(so + ".tmp", so)
+    return so
+
+
 def build_cpp(config="C2", force: bool = False, verbose: bool = False) -> dict:
     """The drop-in C++ MPCPlanner::Solver for one generated solver
     (dimensions are compile-time, as in the reference): codegen into

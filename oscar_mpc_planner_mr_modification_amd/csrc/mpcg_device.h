@@ -383,9 +383,23 @@ __device__ inline void erk_unicycle(const mpcg_problem& pr, const double z[NU + 
 // ---------------------------------------------------------------------------
 // MIRROR: H <- V f(D) V', f(d) = eps if |d| <= eps else |d|, cyclic Jacobi
 // on the nz x nz stage block.  Rotations on exactly-zero couplings are skipped,
-// so decoupled sub-blocks (e.g. {a,w,psi,v} vs {x,y,s} with a zero disc
-// offset) cost only their own rotations.
+// so in the general form decoupled sub-blocks cost only their own rotations,
+// but every rotation still updates all rows of A and V, the sweep test sums
+// all off-diagonals and the reconstruction forms all entries.
+// BLOCKS: the unicycle's block with a zero disc offset is exactly block-diagonal,
+// {a, w, psi, v} = {0, 1, 4, 5} and {x, y, s} = {2, 3, 6} (the cost touches x, y, s
+// and the diagonals, the ERK4 adjoint Hessian zi, and the ellipsoid rows' x psi,
+// y psi, psi psi terms are multiples of the offset).  The BLOCKS form is the same
+// sweep with everything that is an exact zero there left out: the in-block pairs in
+// the same lexicographic order with the same skip, the in-block rows of A and V,
+// the in-block terms of the sweep test (one test over both blocks, as before) and
+// of the reconstruction in the same order, and +0.0 stored to the cross entries
+// (what the general form's 0.0 + (+-0) sums give).  Its operands and operation order
+// are the general form's, so it returns the same bits wherever mirror_blocks_ok holds
+// (tests/test_gpu_mirror_blocks.py); mirror_stage chooses per wave.
 // ---------------------------------------------------------------------------
+// block of index i of the unicycle's leading 7 x 7 block, z = [a w x y psi v s]
+__host__ __device__ constexpr int mirror_blk(int i) { return (i == 2 || i == 3 || i == 6) ? 1 : 0; }
 // dia_extra: squared diagonal of a decoupled block handled outside (it enters
 // the convergence test exactly as in the full-size sweep)
 // NA: the leading NA x NA block of the NZ x NZ array is mirrored in place
@@ -393,17 +407,21 @@ __device__ inline void erk_unicycle(const mpcg_problem& pr, const double z[NU + 
 // (The round-robin, parallel Jacobi ordering measured slower -- profiles/r03q_ab.jsonl: C2 11.97 -> 12.04
 // ms, C1 +1.6 %, C5 +1.3 %, JS +1.2 %; C4 -1.0 % -- and its different rounding moved one C5 copy of 8,192
 // to another exit, 1602: QP failure in the oracle, success on the GPU; profiles/r03q_rr_fullsize.log)
-template <int NZ, int NA = NZ>
+template <int NZ, int NA = NZ, bool BLOCKS = false>
 __device__ inline void mirror(double A[NZ][NZ], double eps, double dia_extra = 0.0) {
+    static_assert(!BLOCKS || NA == 7, "the block form is the unicycle's 7 x 7 block");
     // Cyclic Jacobi on the symmetric part, one-sided rotation updates on the
     // upper triangle (a_pp -= t a_pq, a_qq += t a_pq, off-diagonal pairs with
     // tau = s / (1 + c)); V accumulates the eigenvectors.  Then
     // A = V diag(f(d)) V' with f(d) = eps if |d| <= eps else |d|.
+    // in(i, j): entry (i, j) can be non-zero (BLOCKS: same block; the others are never read)
+    constexpr auto in = [](int i, int j) { return !BLOCKS || mirror_blk(i) == mirror_blk(j); };
     double V[NA][NA];
 #pragma unroll
     for (int i = 0; i < NA; ++i)
 #pragma unroll
         for (int j = 0; j < NA; ++j) {
+            if (!in(i, j)) continue;
             V[i][j] = (i == j) ? 1.0 : 0.0;
             if (j > i) A[i][j] = 0.5 * (A[i][j] + A[j][i]);
         }
@@ -414,13 +432,15 @@ __device__ inline void mirror(double A[NZ][NZ], double eps, double dia_extra = 0
             dia += A[i][i] * A[i][i];
             if (i == NA - 1) dia += dia_extra;
 #pragma unroll
-            for (int j = i + 1; j < NA; ++j) off += A[i][j] * A[i][j];
+            for (int j = i + 1; j < NA; ++j)
+                if (in(i, j)) off += A[i][j] * A[i][j];
         }
         if (off <= 1e-32 * dia || off < 1e-300) break;
 #pragma unroll
         for (int p = 0; p < NA - 1; ++p)
 #pragma unroll
             for (int q = p + 1; q < NA; ++q) {
+                if (!in(p, q)) continue;
                 const double apq = A[p][q];
                 if (fabs(apq) >= 1e-300) {
                     const double theta = 0.5 * (A[q][q] - A[p][p]) * frcp(apq);
@@ -435,7 +455,7 @@ __device__ inline void mirror(double A[NZ][NZ], double eps, double dia_extra = 0
                     A[p][q] = 0.0;
 #pragma unroll
                     for (int r = 0; r < NA; ++r) {
-                        if (r == p || r == q) continue;
+                        if (r == p || r == q || !in(r, p)) continue;
                         double& arp = r < p ? A[r][p] : A[p][r];
                         double& arq = r < q ? A[r][q] : A[q][r];
                         const double g = arp, h = arq;
@@ -444,6 +464,7 @@ __device__ inline void mirror(double A[NZ][NZ], double eps, double dia_extra = 0
                     }
 #pragma unroll
                     for (int r = 0; r < NA; ++r) {
+                        if (!in(r, p)) continue;
                         const double g = V[r][p], h = V[r][q];
                         V[r][p] = g - sn * fma(g, tau, h);
                         V[r][q] = h + sn * fma(-h, tau, g);
@@ -463,10 +484,38 @@ __device__ inline void mirror(double A[NZ][NZ], double eps, double dia_extra = 0
         for (int j = i; j < NA; ++j) {
             double acc = 0.0;
 #pragma unroll
-            for (int k = 0; k < NA; ++k) acc += V[i][k] * d[k] * V[j][k];
+            for (int k = 0; k < NA; ++k)
+                if (in(i, j) && in(i, k)) acc += V[i][k] * d[k] * V[j][k];
             A[i][j] = acc;
             A[j][i] = acc;
         }
+}
+
+// The lane's 7 x 7 block is one the BLOCKS form reproduces bit for bit: its 12 cross-block couplings
+// (both triangles) are exactly zero and what the sweep reads of its two blocks is finite (a NaN or an
+// infinity inside a block reaches the cross entries through the general form's rotations)
+template <int NZ>
+__device__ inline bool mirror_blocks_ok(const double A[NZ][NZ]) {
+    bool ok = true;
+#pragma unroll
+    for (int i = 0; i < 7; ++i)
+#pragma unroll
+        for (int j = i; j < 7; ++j) {
+            if (mirror_blk(i) != mirror_blk(j)) ok &= (A[i][j] == 0.0) & (A[j][i] == 0.0);
+            else ok &= __builtin_isfinite(i == j ? A[i][i] : 0.5 * (A[i][j] + A[j][i]));
+        }
+    return ok;
+}
+
+// MIRROR of a stage block by the active lanes of the wave (the stage lanes): the BLOCKS form if every
+// one of them holds a block it reproduces, else the general form for all -- a wave-uniform branch, so
+// that the wave never runs one form after the other.  Returns whether the BLOCKS form ran.
+template <int NZ, int NA = NZ>
+__device__ inline bool mirror_stage(double A[NZ][NZ], double eps, double dia_extra = 0.0) {
+    const bool blocks = __builtin_amdgcn_ballot_w64(!mirror_blocks_ok<NZ>(A)) == 0;
+    if (blocks) mirror<NZ, NA, true>(A, eps, dia_extra);
+    else mirror<NZ, NA>(A, eps, dia_extra);
+    return blocks;
 }
 
 }  // namespace mpcg

@@ -224,6 +224,23 @@ struct Cfg {
 #define MPCG_RES_CARRY 1
 #endif
     static constexpr bool RES_CARRY = MPCG_RES_CARRY > 0 && MODEL_ == 0 && PARTS == 3 && NX_ == 5;
+    // MIRROR_BLOCKS: the linearisation mirrors the two decoupled blocks of the unicycle's stage Hessian,
+    // {a, w, psi, v} and {x, y, s}, separately wherever every stage lane of the wave holds an exactly
+    // block-diagonal, finite block (a zero disc offset: the bench batches and every shipped config), and
+    // runs the full-size sweep otherwise (mpcg_device.h mirror_stage).  Same operands in
+    // the same order, so the same bits.  On the three-part N <= 20 unicycle instances without the slack
+    // state (C1, C2, the N 10 shape).  Measured against the parent build (three alternating repetitions, every
+    // output of the bench batches bit for bit the same; the records are named in DESIGN.md §3.10): C2 14.58 ->
+    // 14.14 ms, C1 12.56 -> 12.24; the lean HPIPM kernels stay scratch-free (C2 511 -> 512 of 512 registers
+    // per lane, C1 478 -> 478).  The others keep the full-size sweep: with the block form C5's and C4's
+    // kernels spill more (lean HPIPM 80 -> 88 and 180 -> 196 B/lane), JS and JD do not (§3.10).
+    // (MPCG_MIRROR_BLOCKS=0: the full-size sweep everywhere; =2: the block form on every unicycle
+    // instance; A/B and scripts/bitcmp.py)
+#ifndef MPCG_MIRROR_BLOCKS
+#define MPCG_MIRROR_BLOCKS 1
+#endif
+    static constexpr bool MIRROR_BLOCKS =
+        MODEL_ == 0 && (MPCG_MIRROR_BLOCKS >= 2 || (MPCG_MIRROR_BLOCKS == 1 && PARTS == 3 && NX_ == 5));
     // the capsule's QP memory (mpcg_io.qp_in / qp_out, opaque): per slot and lane the row's
     // slack then multiplier ([2 s + {0, 1}][64 lanes]), then the QP step [N+1][NZ] and the
     // dynamics multipliers [N][NX]

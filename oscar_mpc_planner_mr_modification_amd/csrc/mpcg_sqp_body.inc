@@ -330,7 +330,8 @@
                     // coupling): MIRROR of the 8x8 block = MIRROR of the leading 7x7 block
                     // plus the mirrored slack diagonal, with the same sweep count
                     const double hs = H[NZ - 1][NZ - 1];
-                    mirror<NZ, NZ - 1>(H, pr.reg_eps, hs * hs);
+                    if constexpr (C::MIRROR_BLOCKS) mirror_stage<NZ, NZ - 1>(H, pr.reg_eps, hs * hs);
+                    else mirror<NZ, NZ - 1>(H, pr.reg_eps, hs * hs);
                     H[NZ - 1][NZ - 1] = (hs >= -pr.reg_eps && hs <= pr.reg_eps) ? pr.reg_eps : fabs(hs);
                 } else if constexpr (C::MODEL == 1) {
                     // the bicycle's slack input is decoupled the same way (quadratic cost, linear
@@ -357,6 +358,10 @@
                             const int pj2 = j == NZ - 1 ? ZS : (j < ZS ? j : j + 1);
                             H[pi2][pj2] = Hp[i][j];
                         }
+                } else if constexpr (C::MIRROR_BLOCKS) {
+                    // the two decoupled blocks of a zero disc offset mirrored separately, where every stage
+                    // lane of the wave holds such a block (mpcg_device.h mirror_stage; DESIGN.md §3.10)
+                    mirror_stage<NZ>(H, pr.reg_eps);
                 } else {
                     mirror<NZ>(H, pr.reg_eps);
                 }
