@@ -21,9 +21,11 @@ tolerance (rtol 1e-10, atol 1e-9), and the unicycle's ERK4 map (x+, [B A], adjoi
 1e-12: twelve stage evaluations of order-one terms accumulate a few hundred roundings of 1.1e-16,
 and the device's sincos and the C library's differ by an ulp.
 
-h_rows (the inequality rows, mpcg_sqp.h) is lane-structured -- one lane per row group, results in
-LDS -- and cannot be called from a single thread; it is left to tests/test_gpu_geometry.py, which
-runs it with every term non-zero.
+h_rows (the inequality rows, mpcg_sqp.h) is lane-structured -- a lane (stage, part) evaluates the
+rows part + PARTS r of its stage and leaves values and gradients in LDS -- but it takes the lane's
+LaneRows as an argument and could be called per part from a probe, one call for each part.  It is
+nonetheless left to the whole-solve tests: tests/test_gpu_geometry.py runs it with every term
+non-zero, and tests/test_gpu_bounds.py runs the box rows of the same LaneRows binding.
 """
 import ctypes as C
 import os
