@@ -13,6 +13,22 @@ One (scene, planner, stage) at a time, following the reference sources:
                          textbook step z <- (z + R_B(R_A(z))) / 2, parity unpinned
   ellipsoids             ellipsoid_constraints.cpp:34-86
   consistency            guidance_constraints.cpp:986-1023, 1073-1133
+
+and of the bookkeeping between two control steps (`advance`), the checker for
+producers.advance_host and for the device kernel mpcg_advance.  One scene and
+one planner at a time:
+  main warm start        Planner::solveMPC, planner.cpp:129-137: initializeWarmstart(state, shift)
+                         of the winner's output (acados_solver_interface.cpp:344-376; the main
+                         solver holds the winner's _output and _params, guidance_constraints.cpp:520-522)
+                         after a feasible step, else initializeWithBraking (:303-342)
+  previous plan          storePreviousTrajectoryFromSolver, guidance_constraints.cpp:1052-1071,
+                         called at :537; none after an infeasible step (:429-442)
+  consistency flags      shouldEnableConsistencyForPlanner, guidance_constraints.cpp:951-984, on the
+                         selection remembered at :535-540
+  selection flags        OverrideSelectedTrajectory(guidance_ID, clear_selection),
+                         guidance_constraints.cpp:504-518: not called after an infeasible step
+  carried multipliers    each LocalPlanner's capsule keeps them; Solver_acados_reset after a
+                         failed solve (acados_solver_interface.cpp:186-190)
 """
 import math
 
@@ -159,3 +175,127 @@ def prepare(layout, sc, robot_radius, w_consistency, deceleration=3.0, warmstart
                     p[ix("prev_traj_y")] = prev_i[s, k, 1] if on else 0.0
                 params[b, k] = p
     return dict(params=params, warm=warm, xinit=xinit, prev_interp=prev_i, consistency_active=active)
+
+
+_VARS = ("a", "w", "x", "y", "psi", "v", "spline")   # the stage variables z = (u, x) in x0's order
+_NU = 2
+
+
+def _braking_plan(state, N, dt, deceleration):
+    """Solver::initializeWithBraking(state) (acados_solver_interface.cpp:303-342): x0 [N+1][7]"""
+    x0 = np.zeros((N + 1, 7))
+    x, y, psi, v, spline = (float(state[i]) for i in range(5))
+    a = -abs(deceleration)
+    x0[0] = (a, 0.0, x, y, psi, v, spline)
+    for k in range(1, N + 1):
+        x += v * dt * math.cos(psi)
+        y += v * dt * math.sin(psi)
+        spline += v * dt
+        v += a * dt
+        v = max(v, 0.0)
+        x0[k] = (a, 0.0, x, y, psi, v, spline)
+    return x0
+
+
+def _initialize_warmstart(x0, out_x, out_u, state, N, shift):
+    """Solver::initializeWarmstart(state, shift) (acados_solver_interface.cpp:344-376) on x0 [N+1][7],
+    variable by variable; getOutput(k, name) reads xtraj[k] for a state and utraj[k] for an input"""
+    def get_output(k, i):
+        return out_u[k][i] if i < _NU else out_x[k][i - _NU]
+
+    if shift:
+        for k in range(N + 1):
+            for i in range(len(_VARS)):
+                if k == 0:
+                    # State holds no inputs: the reference reads them out of State's range; the
+                    # library defines them as the inputs of out_1 (producers.initialize_warmstart)
+                    x0[0][i] = get_output(1, i) if i < _NU else state[i - _NU]
+                elif k == N - 1:
+                    x0[N - 1][i] = get_output(N - 1, i)
+                elif k == N:
+                    x0[N][i] = get_output(N - 1, i)
+                else:
+                    x0[k][i] = get_output(k + 1, i)
+    else:
+        for k in range(N):
+            for i in range(len(_VARS)):
+                x0[k][i] = get_output(k, i)
+
+
+def advance(layout, best, exit_code, xtraj, utraj, warm, lam_out, state_next, guided, elapsed,
+            deceleration=3.0, shift_forward=False, consistency_on_non_guided=True, topology=None,
+            topology_next=None, previously_selected=None):
+    """What step t leaves for step t + 1 (the arguments of producers.advance_host), as a dict with
+    Carried's fields: main_warm, prev_traj, prev_elapsed, consistency_on, previously_selected, lam."""
+    N, dt = layout.N, layout.dt
+    S, G = np.asarray(guided).shape
+    main_warm = np.zeros((S, N + 1, 7))
+    prev_traj = np.zeros((S, N, 2))
+    prev_elapsed = np.zeros(S)
+    cons_on = np.zeros((S, G), bool)
+    prev_sel = np.zeros((S, G), bool)
+    lam = None if lam_out is None else np.zeros(np.shape(lam_out))
+    for s in range(S):
+        b = int(best[s])
+        # ---- the decision of step t (guidance_constraints.cpp:428-543)
+        if b == -1:
+            was_feasible = False
+            has_previous_trajectory = False
+            prev_selected_topology_id = -1
+            prev_was_original_planner = False
+        else:
+            was_feasible = True
+            sol = s * G + b
+            is_original = not bool(guided[s][b])
+            guidance_id = b if topology is None else int(topology[s][b])
+            clear_selection = is_original
+            # _solver->_output / _params = the best solver's (:520-522)
+            out_x, out_u = xtraj[sol], utraj[sol]
+            x0 = [[float(warm[sol][k][i]) for i in range(7)] for k in range(N + 1)]
+            # storePreviousTrajectoryFromSolver (:1052-1071)
+            for k in range(N):
+                prev_traj[s, k, 0] = out_x[k][0]
+                prev_traj[s, k, 1] = out_x[k][1]
+            has_previous_trajectory = True
+            prev_selected_topology_id = guidance_id
+            prev_was_original_planner = is_original
+        prev_elapsed[s] = elapsed if has_previous_trajectory else math.nan
+        # ---- step t + 1, Planner::solveMPC (planner.cpp:129-137)
+        if was_feasible:
+            _initialize_warmstart(x0, out_x, out_u, state_next[s], N, shift_forward)
+            main_warm[s] = x0
+        else:
+            main_warm[s] = _braking_plan(state_next[s], N, dt, deceleration)
+        for g in range(G):
+            is_guided = bool(guided[s][g])
+            this_topology = g if topology_next is None else int(topology_next[s][g])
+            # OverrideSelectedTrajectory(guidance_ID, clear_selection) (:504-518) marks the guidance
+            # trajectory of that class unless cleared; not called when no planner was feasible, so the
+            # flags of step t stay.  The non-guided planner has no guidance trajectory.
+            if not was_feasible:
+                prev_sel[s, g] = bool(previously_selected[s][g]) if previously_selected is not None else False
+            else:
+                prev_sel[s, g] = is_guided and not clear_selection and this_topology == guidance_id
+            # shouldEnableConsistencyForPlanner (:951-984)
+            if not has_previous_trajectory:
+                on = False
+            elif prev_selected_topology_id == -1 and not prev_was_original_planner:
+                on = False
+            elif not is_guided:
+                on = bool(consistency_on_non_guided) and prev_was_original_planner
+            elif prev_was_original_planner:
+                on = False
+            else:
+                on = this_topology == prev_selected_topology_id
+            cons_on[s, g] = on
+            # the planner's capsule: multipliers kept after a success, reset after a failure
+            # (acados_solver_interface.cpp:183-191)
+            if lam is not None:
+                i = s * G + g
+                if int(exit_code[i]) == 1:
+                    for k in range(N):
+                        lam[i][k] = lam_out[i][k]
+                else:
+                    lam[i] = 0.0
+    return dict(main_warm=main_warm, prev_traj=prev_traj, prev_elapsed=prev_elapsed, consistency_on=cons_on,
+                previously_selected=prev_sel, lam=lam)

@@ -636,7 +636,12 @@ int mpcg_select_best_device(int n_scenes, int n_guesses, int N, const double* xt
                             const unsigned char* consistency_enabled, const unsigned char* previously_selected,
                             double selection_weight, const unsigned char* disabled, int* best, double* objective,
                             void* stream) {
-    if (n_scenes <= 0) return 0;
+    // prev_traj, the flag arrays and objective are optional (include/mpcg.h)
+    if (n_scenes < 0 || n_guesses < 1 || N < 1 || (n_scenes > 0 && (!xtraj || !pobj || !exit_code || !best))) {
+        mpcg::g_err = "mpcg_select_best_device: invalid arguments";
+        return -1;
+    }
+    if (n_scenes == 0) return 0;
     const int T = 64;
     hipLaunchKernelGGL(mpcg::select_best_kernel, dim3((n_scenes + T - 1) / T), dim3(T), 0, (hipStream_t)stream,
                        n_scenes, n_guesses, N, xtraj, pobj, exit_code, prev_traj, w_cons, consistency_enabled,

@@ -289,12 +289,14 @@ def solve_batch_host(pr: MpcgProblem, params: np.ndarray, warm: np.ndarray, xini
 
 def select_best_device(n_scenes, n_guesses, N, xtraj, pobj, exit_code, prev_traj=None, w_cons=0.0,
                        consistency_enabled=None, previously_selected=None, selection_weight=1.0,
-                       disabled=None, stream=None):
+                       disabled=None, stream=None, with_objective: bool = True):
+    """mpcg_select_best_device -> (best, objective); with_objective=False passes no objective
+    buffer (NULL) and returns (best, None)."""
     import torch
 
     dev = pobj.device
     best = torch.empty((n_scenes,), dtype=torch.int32, device=dev)
-    objective = torch.empty((n_scenes * n_guesses,), dtype=torch.float64, device=dev)
+    objective = torch.empty((n_scenes * n_guesses,), dtype=torch.float64, device=dev) if with_objective else None
     s = stream if stream is not None else torch.cuda.current_stream(dev)
     rc = lib.mpcg_select_best_device(n_scenes, n_guesses, N, _ptr(xtraj), _ptr(pobj), _ptr(exit_code),
                                      _ptr(prev_traj), float(w_cons), _ptr(consistency_enabled),
@@ -375,19 +377,32 @@ def prepare_device(pr: MpcgProblem, dsc: dict, robot_radius: float, w_consistenc
 def advance_device(pr: MpcgProblem, S: int, G: int, best, exit_code, xtraj, utraj, warm, lam_out, state_next, guided,
                    elapsed: float, deceleration: float = 3.0, shift_forward: bool = False,
                    consistency_on_non_guided: bool = True, topology=None, topology_next=None,
-                   previously_selected=None, stream=None):
-    """mpcg_advance: the carried state of the next control step (device tensors)."""
+                   previously_selected=None, stream=None, out=None):
+    """mpcg_advance: the carried state of the next control step (device tensors).
+    out: preallocated dict(main_warm, prev_traj, prev_elapsed, consistency_on, previously_selected,
+    lam) to write into; its lam may be None (no multipliers carried) or a tensor also when lam_out
+    is None (the kernel then writes zeros)."""
     import torch
 
     dev = xtraj.device
     N = pr.N
     LS = lam_stride(pr)
-    out = dict(main_warm=torch.empty((S, N + 1, NVAR), dtype=torch.float64, device=dev),
-               prev_traj=torch.empty((S, N, 2), dtype=torch.float64, device=dev),
-               prev_elapsed=torch.empty((S,), dtype=torch.float64, device=dev),
-               consistency_on=torch.empty((S, G), dtype=torch.uint8, device=dev),
-               previously_selected=torch.empty((S, G), dtype=torch.uint8, device=dev),
-               lam=None if lam_out is None else torch.empty((S * G, N, LS), dtype=torch.float64, device=dev))
+    if out is None:
+        out = dict(main_warm=torch.empty((S, N + 1, NVAR), dtype=torch.float64, device=dev),
+                   prev_traj=torch.empty((S, N, 2), dtype=torch.float64, device=dev),
+                   prev_elapsed=torch.empty((S,), dtype=torch.float64, device=dev),
+                   consistency_on=torch.empty((S, G), dtype=torch.uint8, device=dev),
+                   previously_selected=torch.empty((S, G), dtype=torch.uint8, device=dev),
+                   lam=None if lam_out is None else torch.empty((S * G, N, LS), dtype=torch.float64, device=dev))
+    else:
+        shapes = dict(main_warm=(S, N + 1, NVAR), prev_traj=(S, N, 2), prev_elapsed=(S,), consistency_on=(S, G),
+                      previously_selected=(S, G), lam=(S * G, N, LS))
+        for k, shp in shapes.items():
+            t = out[k]
+            if t is None and k == "lam":
+                continue
+            want = torch.uint8 if k in ("consistency_on", "previously_selected") else torch.float64
+            assert tuple(t.shape) == shp and t.dtype == want and t.is_contiguous() and t.device == dev, k
     best32 = best.to(torch.int32).contiguous()
     sio = MpcgStepIo(best32.data_ptr(), exit_code.data_ptr(), xtraj.data_ptr(), utraj.data_ptr(), warm.data_ptr(),
                      None if lam_out is None else lam_out.data_ptr(), state_next.data_ptr(), guided.data_ptr(),

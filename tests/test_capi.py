@@ -177,6 +177,30 @@ def test_problem_from_map_reports_missing_entries(lib):
     assert rc == -1 and b"obstacle 3" in lib.mpcg_last_error()
 
 
+def test_select_best_rejects_invalid_arguments(lib):
+    """mpcg_select_best_device checks its arguments before it launches, as mpcg_winner_records_device and
+    mpcg_select_lowest_cost_device do: -1 with the error text set (no device call is reached)"""
+    vp = C.c_void_p
+    lib.mpcg_select_best_device.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_double, vp, vp,
+                                            C.c_double, vp, vp, vp, vp]
+    lib.mpcg_select_best_device.restype = C.c_int
+    lib.mpcg_last_error.restype = C.c_char_p
+    buf = (C.c_double * 8)()
+    p = C.cast(buf, vp)     # stands for a device pointer: never dereferenced on these paths
+
+    def call(S=1, G=1, N=1, xtraj=p, pobj=p, exit_code=p, best=p):
+        return lib.mpcg_select_best_device(S, G, N, xtraj, pobj, exit_code, None, 0.0, None, None, 1.0, None, best,
+                                           None, None)
+
+    for kw in (dict(S=-1), dict(G=0), dict(N=0), dict(xtraj=None), dict(pobj=None), dict(exit_code=None),
+               dict(best=None)):
+        assert call(**kw) == -1, kw
+        assert b"mpcg_select_best_device" in lib.mpcg_last_error(), kw
+    # no scenes: nothing to do, the buffers may be missing
+    assert call(S=0, xtraj=None, pobj=None, exit_code=None, best=None) == 0
+    assert call(S=0, G=0) == -1
+
+
 def test_product_path_fails_loudly_without_the_hip_library(tmp_path):
     """No CPU fallback: with libmpcg.so absent, importing the binding raises."""
     import sys
