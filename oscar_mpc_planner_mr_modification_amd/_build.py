@@ -160,6 +160,37 @@ def build_mirror_probe(force: bool = False) -> str:
     return so
 
 
+def build_fac_rows_probe(force: bool = False) -> str:
+    """build/probe/libfac_rows_probe.so: the test-only translation unit tests/cpp/fac_rows_probe.hip (one
+    wavefront around erk_unicycle of mpcg_device.h, one (z, pi) per lane; tests/test_gpu_fac_rows_probe.py),
+    compiled with the flags of the kernel instances."""
+    src = os.path.join(ROOT, "tests", "cpp", "fac_rows_probe.hip")
+    out_dir = os.path.join(BUILD, "probe")
+    so = os.path.join(out_dir, "libfac_rows_probe.so")
+    deps = [src, os.path.join(INCLUDE, "mpcg.h"), __file__, os.path.join(CSRC, "mpcg_device.h")]
+    if force or _stale(so, deps):
+        os.makedirs(out_dir, exist_ok=True)
+        obj = _hipcc_obj(src, os.path.join(out_dir, "fac_rows_probe.o"))
+        subprocess.run(["hipcc", f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", so + ".tmp", obj], check=True)
+        os.replace(so + ".tmp", so)
+    return so
+
+
+# the switch-off builds tests/test_gpu_fac_rows.py compares the production library with (DESIGN.md §3.11):
+# name under build/ab/ -> flags.  Only the N <= 20 unicycle family is built in: the test's shapes.
+FAC_AB = {"fac_rows0": ["-DMPCG_FAC_INVARIANT_ROWS=0"],
+          "fac_off": ["-DMPCG_FAC_INVARIANT_ROWS=0", "-DMPCG_FAC_PIVOT_SELECT=0"]}
+
+
+def build_fac_ab(name: str, force: bool = False) -> str:
+    """build/ab/<name>/libmpcg.so: libmpcg.so with FAC_AB[name]'s switches, instances of
+    mpcg_inst_tmpc20.hip only"""
+    out = os.path.join(BUILD, "ab", name, "libmpcg.so")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    return build_lib(force=force, extra_flags=FAC_AB[name], out=out,
+                     sources=("mpcg_kernels.hip", "mpcg_prepare.hip", "mpcg_inst_tmpc20.hip"))
+
+
 def build_cpp(config="C2", force: bool = False, verbose: bool = False) -> dict:
     """The drop-in C++ MPCPlanner::Solver for one generated solver
     (dimensions are compile-time, as in the reference): codegen into

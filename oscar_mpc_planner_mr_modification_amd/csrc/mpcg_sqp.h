@@ -189,6 +189,31 @@ struct Cfg {
     static constexpr bool FCONST = MODEL_ == 0 && N_ >= 30;
     static constexpr int NFR = COMPACT ? 4 : (FCONST ? 2 : NX), NFC = COMPACT ? NZ - 1 : NZ;
     static constexpr int NHP = COMPACT ? (NZ - 1) * NZ / 2 + 1 : NTRI;
+    // FAC_INVARIANT_ROWS: the instances that store every row of [B A] (N <= 20: C1, C2, the N 10 shape)
+    // still hold the same constants in rows psi+, v+, s+ at every stage, so the Riccati loop's prefetch
+    // re-reads only the x+ and y+ rows of the lane's two columns; the constant rows stay in fi / fj from
+    // the fill in front of the loop, which reads every row of stage N-1's block.  The storage (NFR, the
+    // LDS layout) does not change, and the values kept are the bits the re-read would return
+    // (tests/test_fac_invariant_rows.py, tests/test_gpu_fac_rows_probe.py), so the same bits come out
+    // (DESIGN.md §3.11).  Not on the slack model (C5, NX 6: see §3.11).
+    // (MPCG_FAC_INVARIANT_ROWS=0: every row re-read at every stage, A/B and scripts/bitcmp.py)
+#ifndef MPCG_FAC_INVARIANT_ROWS
+#define MPCG_FAC_INVARIANT_ROWS 1
+#endif
+    static constexpr bool FAC_INVARIANT_ROWS =
+        MPCG_FAC_INVARIANT_ROWS > 0 && MODEL_ == 0 && !FCONST && (NX_ == 5 || MPCG_FAC_INVARIANT_ROWS >= 2);
+    // FAC_PIVOT_SELECT: the Riccati step's 2 x 2 pivot block computes the first pivot's reciprocal square
+    // root on every path and selects BLASFEO's zero for a non-positive pivot, as it does for the second
+    // pivot, instead of branching around the Newton chain (mpcg_sqp_body.inc; the same bits, §3.11).  On
+    // the same instances: on the others the FULL variants spill more with it (C5 104 -> 112 B/lane, C4
+    // 244 -> 248, JD 68 -> 72; profiles/r11a_kernel_resources_select_everywhere.txt).
+    // (MPCG_FAC_PIVOT_SELECT=0: the branch everywhere; =2: the select on every NU == 2 instance; A/B and
+    // scripts/bitcmp.py)
+#ifndef MPCG_FAC_PIVOT_SELECT
+#define MPCG_FAC_PIVOT_SELECT 1
+#endif
+    static constexpr bool FAC_PIVOT_SELECT =
+        MPCG_FAC_PIVOT_SELECT >= 2 || (MPCG_FAC_PIVOT_SELECT == 1 && MODEL_ == 0 && !FCONST && NX_ == 5);
     // the vector chains split over the parts of a stage (rows of the backward map, columns of
     // the forward one); the register-starved bicycle instance keeps one owner per stage
     static constexpr bool CHAIN_SPLIT = !COMPACT;

@@ -1017,8 +1017,10 @@
                     for (int m = 0; m < NX; ++m) fi[m] = Fat(N - 1, m, ei);
                     // rows of [B A] that vary over the stages: with the constant rows (FCONST) only x+ and
                     // y+; the others stay in fi / fj from the fill above (their per-stage re-evaluation
-                    // on the lane's runtime column compiled to branches inside the recursion)
-                    constexpr int NFV = C::FCONST ? C::NFR : NX;
+                    // on the lane's runtime column compiled to branches inside the recursion).  The same
+                    // holds where every row is stored (FAC_INVARIANT_ROWS): the stored rows psi+, v+, s+
+                    // are those constants at every stage, and only x+ and y+ are read again
+                    constexpr int NFV = C::FCONST ? C::NFR : (C::FAC_INVARIANT_ROWS ? 2 : NX);
                     // (the compact bicycle storage: its v+ and delta+ rows are the known constants)
                     auto varies = [](int m) { return !C::COMPACT || (m != 3 && m != 4); };
                     // packed Hessian entry of the element lane (the compact storage: slack row / column 0
@@ -1127,8 +1129,18 @@
                             // diagonal and inverse and the column below is multiplied by that zero -- a
                             // failed first pivot leaves l10 = 0, so the second pivot is m11 itself -- and
                             // the recursion goes on; otherwise a failed pivot ends the QP (NaN status)
+                            // (FAC_PIVOT_SELECT: the first reciprocal square root is computed on every
+                            // path and a zero selected for the failed pivot, as for the second: the same
+                            // bits -- the discarded value of a non-positive m00 is never read -- without
+                            // the two basic blocks a branch put in front of the recursion's longest chain)
                             const bool p0 = m00 > 0.0;
-                            const double il00 = (p_pzero && !p0) ? 0.0 : frsq(m00);
+                            double il00;
+                            if constexpr (C::FAC_PIVOT_SELECT) {
+                                const double r00 = frsq(m00);
+                                il00 = (p_pzero && !p0) ? 0.0 : r00;
+                            } else {
+                                il00 = (p_pzero && !p0) ? 0.0 : frsq(m00);
+                            }
                             const double det = fma(m00, m11, -(m10 * m10));
                             const double dd = (p_pzero && !p0) ? m11 : det;
                             const double ild = frsq(dd);
