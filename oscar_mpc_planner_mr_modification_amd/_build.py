@@ -18,8 +18,9 @@ ARCH = os.environ.get("MPCG_OFFLOAD_ARCH", "gfx950")
 SOURCES = {"mpcg_kernels.hip": [], "mpcg_prepare.hip": ["-ffp-contract=off"],
            # built-in kernel instances, one translation unit per family (compiled in parallel)
            "mpcg_inst_tmpc20.hip": [], "mpcg_inst_tmpc30.hip": [], "mpcg_inst_shmpc.hip": [],
-           "mpcg_inst_bicycle.hip": []}
-HEADERS = ["mpcg_device.h", "mpcg_sqp.h", "mpcg_sqp_body.inc", "mpcg_prepare.h", "mpcg_bicycle.h", "mpcg_instance.h"]
+           "mpcg_inst_bicycle.hip": [], "mpcg_inst_road.hip": []}
+HEADERS = ["mpcg_device.h", "mpcg_sqp.h", "mpcg_sqp_body.inc", "mpcg_prepare.h", "mpcg_braking.h", "mpcg_bicycle.h",
+           "mpcg_instance.h"]
 # the multi-robot layer (include/mpcg_fleet.h): linked into libmpcg.so but kept out of SOURCES / HEADERS,
 # whose source_hash() is the identity the committed counter profiles (profiles/traffic_*.json) were taken on
 FLEET_SOURCES = {"mpcg_fleet.hip": ["-ffp-contract=off"]}
@@ -33,6 +34,10 @@ GUIDANCE_HEADERS = ["mpcg_guidance.h"]
 # the active-solve compaction (include/mpcg_active.h): linked in the same way, outside source_hash()
 ACTIVE_SOURCES = {"mpcg_active.hip": ["-ffp-contract=off"]}
 ACTIVE_HEADERS = ["mpcg_active.h"]
+# the road-boundary halfspaces (include/mpcg_road.h): linked in the same way, outside source_hash();
+# mpcg_spline.h is the path evaluation it shares with mpcg_path.h
+ROAD_SOURCES = {"mpcg_road.hip": ["-ffp-contract=off"]}
+ROAD_HEADERS = ["mpcg_road.h", "mpcg_spline.h"]
 HOST_SOURCES = ["host/mpcg_yaml.cpp", "host/mpcg_solver.cpp"]
 HOST_HEADERS = ["mpc_planner_solver/mpcg_yaml.h", "mpc_planner_solver/mpcg_config.h", "mpc_planner_solver/state.h",
                 "mpc_planner_solver/mpcg_solver_interface.h", "mpc_planner_solver/solver_interface.h"]
@@ -66,12 +71,12 @@ def build_lib(force: bool = False, verbose: bool = False, extra_flags=(), out: s
     """libmpcg.so (or a diagnostic / variant build of it with extra_flags at `out`; `sources`
     restricts the built-in instance files of such a build)"""
     srcs = SOURCES if sources is None else {k: v for k, v in SOURCES.items() if k in sources}
-    srcs = {**srcs, **FLEET_SOURCES, **PATH_SOURCES, **GUIDANCE_SOURCES, **ACTIVE_SOURCES}
+    srcs = {**srcs, **FLEET_SOURCES, **PATH_SOURCES, **GUIDANCE_SOURCES, **ACTIVE_SOURCES, **ROAD_SOURCES}
     deps = [os.path.join(CSRC, s) for s in list(SOURCES) + HEADERS + list(FLEET_SOURCES) + FLEET_HEADERS +
             list(PATH_SOURCES) + PATH_HEADERS + list(GUIDANCE_SOURCES) + GUIDANCE_HEADERS +
-            list(ACTIVE_SOURCES) + ACTIVE_HEADERS] + \
+            list(ACTIVE_SOURCES) + ACTIVE_HEADERS + list(ROAD_SOURCES) + ROAD_HEADERS] + \
         [os.path.join(INCLUDE, h) for h in ("mpcg.h", "mpcg_fleet.h", "mpcg_path.h", "mpcg_guidance.h",
-                                            "mpcg_active.h")] + [__file__]
+                                            "mpcg_active.h", "mpcg_road.h")] + [__file__]
     if not force and not _stale(out, deps):
         return out
     objdir = os.path.join(BUILD, "obj" + ("_" + "_".join(f.strip("-").replace("=", "") for f in extra_flags)

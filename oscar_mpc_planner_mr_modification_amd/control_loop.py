@@ -2,7 +2,9 @@
 GuidanceConstraints::optimize and Planner::solveMPC do per step, with every
 per-step quantity device-resident.
 
-    step():  mpcg_prepare (per-guess inputs) -> mpcg_solve (all guesses, carried
+    step():  mpcg_prepare (per-guess inputs) [-> with a road mpcg_road_halfspaces: the two
+             road rows into the prepared parameters, before skip_disabled's gather too]
+             -> mpcg_solve (all guesses, carried
              multipliers; with skip_disabled mpcg_solve_active: the enabled guesses only)
              -> mpcg_select_best_device (FindBestPlanner with the
              consistency / selection-weight bookkeeping) -> mpcg_advance (warm
@@ -22,7 +24,8 @@ class ControlLoop:
     def __init__(self, layout: Layout, scenes, device, robot_radius: float, w_consistency: float,
                  selection_weight: float, deceleration: float = 3.0, shift_forward: bool = False,
                  consistency_on_non_guided: bool = True, elapsed: float | None = None,
-                 warmstart_with_mpc_solution: bool = False, guidance_layer=None, skip_disabled: bool = False):
+                 warmstart_with_mpc_solution: bool = False, guidance_layer=None, skip_disabled: bool = False,
+                 road=None):
         import torch
 
         if skip_disabled and guidance_layer is None:
@@ -50,6 +53,26 @@ class ControlLoop:
         # One host synchronisation per step (the count of enabled planners); step() adds n_active.
         self.skip_disabled = bool(skip_disabled)
         self.active_ws = native.ActiveWorkspace(self.pr, self.S * self.G, with_lam=True) if self.skip_disabled else None
+        # roads.RoadSettings or None: with a road, every step writes the two road-boundary halfspaces
+        # (include/mpcg_road.h) into the prepared parameters; the path they follow comes from
+        # set_road_path (a PathLoop passes its own).  None: nothing is launched
+        self.road = road
+        self.road_table = self.road_bounds = self.road_halfspaces = None
+        if road is not None:
+            if layout.n_lin < layout.max_obstacles + 2:
+                raise ValueError(f"ControlLoop: a road needs n_lin >= max_obstacles + 2, the layout has n_lin "
+                                 f"{layout.n_lin} for {layout.max_obstacles} obstacles (tmpc_layout(add_halfspaces=2))")
+            self._road = road.native()
+            self.road_halfspaces = torch.zeros((self.S, layout.N, 2, 3), dtype=torch.float64, device=device)
+
+    def set_road_path(self, dtable: dict, bounds: dict | None = None):
+        """The path the road follows (native.path_table_device) and, for the bounds mode, the left and
+        right bound tables (native.road_bounds_device)."""
+        if self.road is None:
+            raise ValueError("ControlLoop.set_road_path: the loop has no road")
+        if self.road.mode == "bounds" and bounds is None:
+            raise ValueError("ControlLoop.set_road_path: the bounds mode needs the bound tables")
+        self.road_table, self.road_bounds = dtable, bounds if self.road.mode == "bounds" else None
 
     def set_scene_data(self, state, obst, guidance, existing_guidance=None):
         """Replace the externally provided scene data (device tensors or arrays).
@@ -72,7 +95,8 @@ class ControlLoop:
 
     def step(self, stream=None):
         """One control step of every scene.  Returns dict(best, exit, xtraj, utraj, pobj, objective, prepared)
-        (plus n_active, the number of planners solved, with skip_disabled)."""
+        (plus n_active, the number of planners solved, with skip_disabled, and road_halfspaces (S, N, 2, 3) with
+        a road)."""
         pr, S, G, N = self.pr, self.S, self.G, self.lay.N
         gl = self.guidance_layer
         if gl is not None:
@@ -84,6 +108,13 @@ class ControlLoop:
                 self.dsc["existing_guidance"] = gl.existing_guidance
         prep = native.prepare_device(pr, self.dsc, self.rr, self.wc, self.dec, stream=stream,
                                      warmstart_with_mpc_solution=self.own_warm, shift_forward=self.shift)
+        if self.road is not None:
+            if self.road_table is None:
+                raise RuntimeError("ControlLoop.step: the loop has a road but no path (set_road_path)")
+            native.road_halfspaces_device(pr, G, self.lay.max_obstacles, self._road, self.road_table, prep["params"],
+                                          state=self.dsc["state"], main_warm=self.dsc.get("main_warm"),
+                                          guided=self.dsc["guided"], deceleration=self.dec, bounds=self.road_bounds,
+                                          halfspaces=self.road_halfspaces, stream=stream)
         if self.skip_disabled:
             out = native.solve_active_device(pr, prep["params"], prep["warm"], prep["xinit"], gl.enabled.reshape(-1),
                                              ws=self.active_ws, stream=stream, lam_in=self.lam, lam_out=True)
@@ -101,6 +132,8 @@ class ControlLoop:
                          objective=objective, prepared=prep, lam=out["lam"])
         if self.skip_disabled:
             self.last["n_active"] = out["n_active"]
+        if self.road is not None:
+            self.last["road_halfspaces"] = self.road_halfspaces
         if gl is not None:
             gl.after_select(self, self.last, stream=stream)
         return self.last

@@ -18,38 +18,18 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/mpcg_path.h"  // the public header of the same name
+#include "mpcg_spline.h"              // PathLds, path_segment, path_point
 
 namespace mpcg {
 
-constexpr int PATH_MAX_M = MPCG_PATH_MAX_SEGMENTS;
 constexpr int PATH_LANES = MPCG_PATH_SAMPLES;
 constexpr int PATH_ROUNDS = MPCG_PATH_ROUNDS;
 constexpr double PATH_LAST = (double)(PATH_LANES - 1);
-
-struct PathLds {
-    double knots[PATH_MAX_M + 1];
-    double coef[PATH_MAX_M][8];
-};
 
 // sample i of the bracket [lo, hi]
 __device__ __forceinline__ double path_sample(double lo, double hi, int i) {
     const double w = __dsub_rn(hi, lo);
     return fmin(__dadd_rn(lo, __ddiv_rn(__dmul_rn(w, (double)i), PATH_LAST)), hi);
-}
-
-// the segment that holds s: the last j < m with knots[j] <= s (0 before the path, m - 1 beyond it)
-__device__ __forceinline__ int path_segment(const PathLds& L, int m, double s) {
-    int j = 0;
-    for (int k = 1; k < m; ++k) j += L.knots[k] <= s ? 1 : 0;
-    return j;
-}
-
-// the point of segment j at s
-__device__ __forceinline__ void path_point(const PathLds& L, int j, double s, double& x, double& y) {
-    const double t = __dsub_rn(s, L.knots[j]);
-    const double* c = L.coef[j];
-    x = __dadd_rn(__dmul_rn(__dadd_rn(__dmul_rn(__dadd_rn(__dmul_rn(c[0], t), c[1]), t), c[2]), t), c[3]);
-    y = __dadd_rn(__dmul_rn(__dadd_rn(__dmul_rn(__dadd_rn(__dmul_rn(c[4], t), c[5]), t), c[6]), t), c[7]);
 }
 
 // |p - q|^2, a NaN counting as +inf (a total order for the arg-min)

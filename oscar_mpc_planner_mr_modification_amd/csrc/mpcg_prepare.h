@@ -24,6 +24,7 @@
 #include <hip/hip_runtime.h>
 
 #include "mpcg.h"
+#include "mpcg_braking.h"
 
 namespace mpcg {
 
@@ -83,19 +84,10 @@ __global__ __launch_bounds__(64) void prepare_kernel(mpcg_problem pr, int n_scen
         for (int e = lane; e < (N + 1) * MPCG_NVAR; e += 64) (&L.warm[0][0])[e] = mw[e];
     } else if (lane == 0) {
         // Solver::initializeWithBraking
-        double x = st[0], y = st[1], psi = st[2], v = st[3], s = st[4];
-        const double a = -fabs(in.deceleration);
-        const double c = cos(psi), sn = sin(psi);
-        double* w = L.warm[0];
-        w[0] = a; w[1] = 0.0; w[2] = x; w[3] = y; w[4] = psi; w[5] = v; w[6] = s;
-        for (int k = 1; k <= N; ++k) {
-            x = __dadd_rn(x, __dmul_rn(__dmul_rn(v, dt), c));
-            y = __dadd_rn(y, __dmul_rn(__dmul_rn(v, dt), sn));
-            s = __dadd_rn(s, __dmul_rn(v, dt));
-            v = fmax(__dadd_rn(v, __dmul_rn(a, dt)), 0.0);
-            w = L.warm[k];
+        braking_plan(st, in.deceleration, dt, N, [&](int k, double a, double x, double y, double psi, double v, double s) {
+            double* w = L.warm[k];
             w[0] = a; w[1] = 0.0; w[2] = x; w[3] = y; w[4] = psi; w[5] = v; w[6] = s;
-        }
+        });
     }
     __syncthreads();
     // t-mpc.warmstart_with_mpc_solution (guidance_constraints.cpp:335-338): a guided planner whose

@@ -24,9 +24,11 @@
     // 37.25 -> 37.13), so three-part instances only; and not on the slack model, where it was neutral
     // in time but moved the allocation into scratch (C5 52 -> 188 B/lane, 264 -> 782 MB of HBM traffic
     // per launch, profiles/r03u_c5_pmc.json).
-    constexpr bool RES_SPLIT = !C::COMPACT && 2 * NB <= NZ && PARTS == 3 && NX == 5;
+    // Not on the LEAN storage: the split passes read the dynamics multipliers from S.pin, which LEAN keeps in
+    // the stage lane's registers, so a three-part unicycle shape whose h rows push it over the LDS line (N 20
+    // with 8 obstacles and the two road rows, C2R) runs the single-owner passes (DESIGN.md §6.7).
+    constexpr bool RES_SPLIT = !C::COMPACT && 2 * NB <= NZ && PARTS == 3 && NX == 5 && !LEAN;
     constexpr int DRS = (NX + PARTS - 1) / PARTS;  // dynamics rows per part
-    static_assert(!(RES_SPLIT && LEAN), "the split passes read the dynamics multipliers from S.pin");
     // the next iterate's residual products formed in the refinement test's pass (C::RES_CARRY, mpcg_sqp.h):
     // the split passes only
     constexpr bool RES_CARRY = C::RES_CARRY && RES_SPLIT && !LEAN;

@@ -269,6 +269,12 @@ def config_layout(cfg: str) -> Layout:
         # max_obstacles 5 (mpc_planner_jackal/config/settings.yaml:3,38, mpc_planner_dingo :2,33),
         # n_paths 4 -> 5 planners (:102)
         return tmpc_layout(N=30, max_obstacles=5, name="JD")
+    if cfg == "C2R":
+        # C2 with the two road-boundary halfspaces (add_halfspaces 2, guidance_constraints.py:37-41)
+        return tmpc_layout(N=20, max_obstacles=8, add_halfspaces=2, name="C2R")
+    if cfg == "JSR":
+        # the shipped jackalsimulator solver with the road rows its settings.yaml intends
+        return tmpc_layout(N=30, max_obstacles=4, add_halfspaces=2, name="JSR")
     if cfg == "C5":
         lay = safe_horizon_layout(N=20, n_constraints=24)
         lay.name = "C5"

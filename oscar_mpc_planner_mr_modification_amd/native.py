@@ -14,8 +14,8 @@ from .native_spec import (ABI_VERSION, ACTIVE_EXPORTS, DEFAULT_OPTIONS, EXPORTS,
                           GUIDANCE_CANDIDATES,
                           GUIDANCE_EXPORTS, INFO_STRIDE, NU, NVAR, NX, PATH_EXPORTS, STATS_STRIDE, UNICYCLE_LB,
                           UNICYCLE_UB, MpcgFleetSettings, MpcgFleetState, MpcgGuidanceOut, MpcgGuidanceSettings,
-                          MpcgGuidanceState, MpcgIo, MpcgPathSettings, MpcgPathTable, MpcgProblem, MpcgSceneIo,
-                          MpcgStepIo, MpcgScenarioIo, problem_from_layout)
+                          MpcgGuidanceState, MpcgIo, MpcgPathSettings, MpcgPathTable, MpcgProblem, MpcgRoadIo,
+                          MpcgRoadSettings, MpcgSceneIo, MpcgStepIo, MpcgScenarioIo, ROAD_EXPORTS, problem_from_layout)
 
 PKG = os.path.dirname(os.path.abspath(__file__))
 # MPCG_LIB selects a diagnostic build (e.g. libmpcg_stamps.so); default the production library
@@ -84,6 +84,10 @@ def _load():
     lib.mpcg_path_command.argtypes = [P, C.c_int, C.c_int, C.POINTER(MpcgPathSettings), vp, vp, vp, vp, vp, C.c_int,
                                       vp, vp, vp]
     lib.mpcg_path_command.restype = C.c_int
+    # include/mpcg_road.h
+    lib.mpcg_road_halfspaces.argtypes = [P, C.c_int, C.c_int, C.c_int, C.POINTER(MpcgRoadSettings),
+                                         C.POINTER(MpcgPathTable), vp, C.POINTER(MpcgRoadIo), vp, vp, vp]
+    lib.mpcg_road_halfspaces.restype = C.c_int
     # include/mpcg_guidance.h
     lib.mpcg_guidance_update.argtypes = [P, C.c_int, C.c_int, C.POINTER(MpcgGuidanceSettings), vp, vp, vp, vp,
                                          C.POINTER(MpcgGuidanceState), C.POINTER(MpcgGuidanceOut), vp]
@@ -588,6 +592,45 @@ def path_command_device(pr: MpcgProblem, G: int, settings: MpcgPathSettings, bes
                                _ptr(closest_s), int(spline_slot), _ptr(cmd), _ptr(state_next),
                                C.c_void_p(s.cuda_stream))
     _check(rc, "mpcg_path_command")
+
+
+def road_bounds_device(left_coef, right_coef, device) -> dict:
+    """The bound tables (P, M, 8) of the bounds mode (roads.stack_bounds) as device tensors."""
+    import torch
+
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float64)).to(device)  # noqa: E731
+    return dict(left=t(left_coef), right=t(right_coef))
+
+
+def road_halfspaces_device(pr: MpcgProblem, G: int, max_obstacles: int, settings: MpcgRoadSettings, dtable: dict,
+                           params, state=None, main_warm=None, guided=None, deceleration: float = 3.0, bounds=None,
+                           halfspaces=None, stream=None):
+    """mpcg_road_halfspaces (include/mpcg_road.h): the two road rows of the stages 1 .. N-1 into
+    params (S*G, N, npar) as mpcg_prepare left it -- rows max_obstacles.. of the guided planners
+    (guided (S, G) uint8), rows 0, 1 of the others -- at the `spline` entries of main_warm
+    (S, N+1, 7), or of the braking plan from state (S, nx) when it is None.  `dtable`:
+    path_table_device; `bounds`: road_bounds_device, for the bounds mode; halfspaces (S, N, 2, 3),
+    optional, receives the rows per scene.  Asynchronous on `stream`; nothing is allocated."""
+    import torch
+
+    S, N = dtable["path_of"].numel(), pr.N
+    assert tuple(params.shape) == (S * G, N, pr.npar)
+    for t_ in (params, state, main_warm, halfspaces) + ((bounds["left"], bounds["right"]) if bounds else ()):
+        assert t_ is None or (t_.dtype == torch.float64 and t_.is_cuda and t_.is_contiguous())
+    assert state is None or tuple(state.shape) == (S, pr.nx)
+    assert main_warm is None or tuple(main_warm.shape) == (S, N + 1, pr.nu + pr.nx)
+    assert guided is None or (guided.dtype == torch.uint8 and guided.is_contiguous() and guided.numel() == S * G)
+    assert halfspaces is None or tuple(halfspaces.shape) == (S, N, 2, 3)
+    if bounds:
+        assert tuple(bounds["left"].shape) == tuple(dtable["coef"].shape) == tuple(bounds["right"].shape)
+    io = MpcgRoadIo(None if state is None else state.data_ptr(), None if main_warm is None else main_warm.data_ptr(),
+                    float(deceleration), None if guided is None else guided.data_ptr(),
+                    bounds["left"].data_ptr() if bounds else None, bounds["right"].data_ptr() if bounds else None)
+    s = stream if stream is not None else torch.cuda.current_stream(params.device)
+    rc = lib.mpcg_road_halfspaces(C.byref(pr), S, G, int(max_obstacles), C.byref(settings), C.byref(dtable["native"]),
+                                  dtable["path_of_host"].ctypes.data, C.byref(io), _ptr(params), _ptr(halfspaces),
+                                  C.c_void_p(s.cuda_stream))
+    _check(rc, "mpcg_road_halfspaces")
 
 
 def _guidance_state(gstate: dict, S: int, G: int, N: int) -> MpcgGuidanceState:

@@ -203,6 +203,22 @@ PATH_MAX_SEGMENTS, PATH_SAMPLES, PATH_ROUNDS, PATH_REACHED_RADIUS = 64, 64, 5, 1
 
 
 
+class MpcgRoadSettings(C.Structure):
+    """Mirror of `mpcg_road_settings` (include/mpcg_road.h)."""
+    _fields_ = [("width", C.c_double), ("robot_radius", C.c_double), ("two_way", C.c_int), ("mode", C.c_int)]
+
+
+class MpcgRoadIo(C.Structure):
+    """Mirror of `mpcg_road_io` (include/mpcg_road.h)."""
+    _fields_ = [("state", C.c_void_p), ("main_warm", C.c_void_p), ("deceleration", C.c_double),
+                ("guided", C.c_void_p), ("left_coef", C.c_void_p), ("right_coef", C.c_void_p)]
+
+
+# the road-boundary halfspaces (include/mpcg_road.h), exported from the same library
+ROAD_EXPORTS = ("mpcg_road_halfspaces",)
+ROAD_CENTERLINE, ROAD_BOUNDS, ROAD_MAX_N = 0, 1, 32
+
+
 class MpcgGuidanceSettings(C.Structure):
     """Mirror of `mpcg_guidance_settings` (include/mpcg_guidance.h)."""
     _fields_ = [("robot_radius", C.c_double), ("v_ref", C.c_double), ("consistency_on_non_guided", C.c_int)]

@@ -266,10 +266,15 @@ class PathLoop:
     or a `FleetLoop`'s launches around the same scenes), unless the loop has a guidance layer
     (loop_options guidance_layer=guidance.GuidanceLayer): the path update runs before the layer's
     update inside ControlLoop.step, because the layer's nominal needs this step's window.  With the
-    layer, loop_options skip_disabled=True leaves the planners it disables unsolved."""
+    layer, loop_options skip_disabled=True leaves the planners it disables unsolved.
+
+    road=roads.RoadSettings: the loop's steps also write the two road-boundary halfspaces along the
+    tracked paths (include/mpcg_road.h); the bounds mode takes its bound tables (P, M, 8) through
+    `set_path`.  road=None: nothing is launched."""
 
     def __init__(self, layout, scenes, table: PathTable, path_of, device, settings: PathSettings, robot_radius: float,
-                 w_consistency: float, selection_weight: float, spline_slot: int | None = None, **loop_options):
+                 w_consistency: float, selection_weight: float, spline_slot: int | None = None, road=None,
+                 left_coef=None, right_coef=None, **loop_options):
         import torch
 
         from . import native
@@ -278,7 +283,8 @@ class PathLoop:
         if len(path_of) != scenes.n_scenes:
             raise ValueError(f"path_of has {len(path_of)} entries for {scenes.n_scenes} scenes")
         loop_options.setdefault("deceleration", settings.deceleration)
-        self.loop = ControlLoop(layout, scenes, device, robot_radius, w_consistency, selection_weight, **loop_options)
+        self.loop = ControlLoop(layout, scenes, device, robot_radius, w_consistency, selection_weight, road=road,
+                                **loop_options)
         self.settings, self._set = settings, settings.native()
         self.spline_slot = layout.nx - 1 if spline_slot is None else spline_slot
         S = scenes.n_scenes
@@ -288,13 +294,18 @@ class PathLoop:
         self.cmd = torch.zeros((S, 2), dtype=torch.float64, device=device)
         self.state_next = torch.zeros((S, layout.nx), dtype=torch.float64, device=device)
         self._native = native
-        self.set_path(table, path_of)
+        self.set_path(table, path_of, left_coef, right_coef)
 
-    def set_path(self, table: PathTable, path_of):
+    def set_path(self, table: PathTable, path_of, left_coef=None, right_coef=None):
         """New paths (onDataReceived): every scene's closest_segment is reset to -1, so the next update
-        searches its whole path."""
+        searches its whole path.  left_coef / right_coef (P, M, 8): the bound splines over the paths' knots
+        (roads.fit_bounds, roads.stack_bounds), read by a road in the bounds mode."""
         self.table = self._native.path_table_device(table, path_of, self.loop.dev)
         self.closest_segment.fill_(-1)
+        if self.loop.road is not None:
+            both = left_coef is not None and right_coef is not None
+            self.loop.set_road_path(self.table, self._native.road_bounds_device(left_coef, right_coef, self.loop.dev)
+                                    if both else None)
 
     def step(self, stream=None):
         """One control step of every scene.  Returns ControlLoop.step's dict plus closest_segment,

@@ -1,0 +1,267 @@
+"""Road-boundary halfspaces on the host (roads.py; include/mpcg_road.h): known answers derived by hand,
+the placement into the planners' lin_constraint rows, the host restatement against the plain-loop
+reference of tests/road_reference.py bit for bit, and the built-in road instances (host-only
+queries of libmpcg.so: without this layer the library has no C2R / JSR shape and no
+mpcg_road_halfspaces)."""
+import ctypes as C
+import os
+
+import numpy as np
+import pytest
+
+import road_cases as rc
+import road_reference as ref
+from oscar_mpc_planner_mr_modification_amd import paths, producers, roads
+from oscar_mpc_planner_mr_modification_amd.layouts import config_layout, tmpc_layout
+from oscar_mpc_planner_mr_modification_amd.synthetic import DECELERATION, ROBOT_RADIUS, SETTINGS_WEIGHTS, make_scenes
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, "oscar_mpc_planner_mr_modification_amd")
+R = 0.325
+
+
+def _straight(p0, p1, n=4):
+    t = np.linspace(0.0, 1.0, n + 1)
+    return paths.fit_path(p0[0] + (p1[0] - p0[0]) * t, p0[1] + (p1[1] - p0[1]) * t)
+
+
+def _rows(road, path, cur_s, left=None, right=None):
+    table = paths.PathTable.from_paths([path])
+    lc = rc_ = None
+    if left is not None:
+        lc, rc_ = roads.stack_bounds(table, [left]), roads.stack_bounds(table, [right])
+    return roads.road_halfspaces_host(road, table, [0], np.asarray(cur_s, float)[None], lc, rc_)[0]
+
+
+def test_straight_path_along_x():
+    """W = 6, r = 0.325 on the path y = 0 along +x: left (0, 1, 2.675), right (0, -1, 2.675) at every stage"""
+    hs = _rows(roads.RoadSettings(6.0, False, R), _straight((0, 0), (20, 0)), np.linspace(0.5, 9.5, 11))
+    assert (hs[0] == 0).all()
+    for k in range(1, 10):
+        assert hs[k, 0].tolist() == [0.0, 1.0, 2.675] and hs[k, 1].tolist() == [0.0, -1.0, 2.675], (k, hs[k])
+
+
+def test_two_way_moves_the_left_row_only():
+    hs = _rows(roads.RoadSettings(6.0, True, R), _straight((0, 0), (20, 0)), np.linspace(0.5, 9.5, 11))
+    for k in range(1, 10):
+        assert hs[k, 0].tolist() == [0.0, 1.0, 8.675] and hs[k, 1].tolist() == [0.0, -1.0, 2.675]
+
+
+def test_path_along_y_points_the_normal_to_minus_x():
+    """travelling along +y the left side is -x: n = (-1, 0); the path x = 0"""
+    hs = _rows(roads.RoadSettings(6.0, False, R), _straight((0, 0), (0, 20)), np.linspace(0.5, 9.5, 11))
+    for k in range(1, 10):
+        # left: -x <= 2.675, right: x <= 2.675
+        assert hs[k, 0].tolist() == [-1.0, 0.0, 2.675] and hs[k, 1].tolist() == [1.0, 0.0, 2.675], (k, hs[k])
+
+
+def test_bounds_mode_on_parallel_straight_bounds():
+    """Straight bounds at y = -2 and y = +2 around a path along +x.  The formulas as the reference
+    has them (contouring.cpp:255-262), b_l = A_l . (p_l + A_l r), b_r = A_r . (p_r - A_r r) with each
+    bound's own orthogonal, give b_l = -(2 - r) and b_r = +(2 - r) -- the corridor |y| <= 2 - r --
+    when the bound passed as `left` lies on the -n side.  With n = (-dy, dx) that is the side right
+    of travel: the sign of getOrthogonal is unpinned (roads.py), and with the bounds handed over
+    the other way round the same formulas shut the road (rows at 2 + r facing outwards)."""
+    centre = _straight((0, 0), (20, 0))
+    K = centre["knots"]
+    at = lambda y: np.stack([K, np.full(len(K), y)], 1)  # noqa: E731
+    road = roads.RoadSettings(6.0, False, R, mode="bounds")
+    cur = np.linspace(0.5, 9.5, 11)
+    left, right = roads.fit_bounds(centre, at(-2.0), at(2.0))
+    hs = _rows(road, centre, cur, left, right)
+    for k in range(1, 10):
+        # row 0 = (-A_l, -b_l): -y <= 2 - r;  row 1 = (A_r, b_r): y <= 2 - r
+        assert hs[k, 0].tolist() == [0.0, -1.0, 2.0 - R] and hs[k, 1].tolist() == [0.0, 1.0, 2.0 - R], (k, hs[k])
+    left, right = roads.fit_bounds(centre, at(2.0), at(-2.0))
+    hs = _rows(road, centre, cur, left, right)
+    for k in range(1, 10):
+        assert hs[k, 0].tolist() == [0.0, -1.0, -(2.0 + R)] and hs[k, 1].tolist() == [0.0, 1.0, -(2.0 + R)], (k, hs[k])
+
+
+def test_cur_s_past_the_end_clamps_to_the_end_point():
+    path = _straight((0, 0), (20, 0))
+    road = roads.RoadSettings(6.0, False, R)
+    cur = np.array([0.0, 19.0, 20.0, 25.0, 1e9, -3.0, np.nan])
+    hs = _rows(road, path, cur)
+    at_end = _rows(road, path, [0.0, 20.0, 20.0])[1]
+    for k in (2, 3, 4):
+        np.testing.assert_array_equal(hs[k], at_end)
+    at_start = _rows(road, path, [0.0, 0.0, 0.0])[1]
+    np.testing.assert_array_equal(hs[5], at_start)
+    # on a curved path the rows at the end differ from the ones before it, so the clamp is visible
+    curved = paths.fit_path([0, 3, 6, 8], [0, 0.5, 2.0, 4.5])
+    L = curved["knots"][-1]
+    h2 = _rows(road, curved, [0.0, L - 0.5, L, L + 4.0])
+    np.testing.assert_array_equal(h2[2], _rows(road, curved, [0.0, L, L, L])[1])
+    assert not np.array_equal(h2[1], h2[2])
+
+
+def test_orthogonal_is_unit_and_left_of_travel():
+    c = rc.kernel_case("C2R-center-warm")
+    hs = roads.road_halfspaces_host(c.road, c.table, c.path_of, c.cur_s)
+    for s in range(c.S):
+        for k in range(1, c.lay.N):
+            n = hs[s, k, 0, :2]
+            assert abs(np.hypot(*n) - 1.0) <= 1e-15
+            np.testing.assert_array_equal(hs[s, k, 1, :2], -n)
+            sk = min(max(c.cur_s[s, k], c.table.knots[c.path_of[s], 0]),
+                     c.table.knots[c.path_of[s], c.table.n_segments[c.path_of[s]]]) if c.cur_s[s, k] == c.cur_s[s, k] \
+                else c.table.knots[c.path_of[s], 0]
+            _, tan, nrm = __import__("path_cases").eval_path(c.tab[c.path_of[s]], sk)
+            assert np.abs(n - nrm).max() <= 1e-12 and tan[0] * n[1] - tan[1] * n[0] > 0.99
+
+
+@pytest.mark.parametrize("name", list(rc.KERNEL_CASES))
+def test_host_equals_the_plain_loop_reference_bit_for_bit(name):
+    c = rc.kernel_case(name)
+    lay = c.lay
+    cur = c.cur_s
+    if c.main_warm is None:
+        want = [ref.braking_spline(c.state[s], lay.N, lay.dt, DECELERATION) for s in range(c.S)]
+        np.testing.assert_array_equal(cur, np.array(want))
+    hs = roads.road_halfspaces_host(c.road, c.table, c.path_of, cur, c.left, c.right)
+    want = ref.road_halfspaces_reference(c.road.width, c.road.two_way, c.road.robot_radius, c.road.mode, c.table.coef,
+                                         c.table.knots, c.table.n_segments, c.path_of, cur, c.left, c.right)
+    assert np.isfinite(hs).all()
+    np.testing.assert_array_equal(hs.view(np.int64), want.view(np.int64))
+    got = roads.apply_road_host(lay, c.params, c.guided, hs)
+    placed = ref.apply_road_reference(lay.N, lay.npar, lay.idx("lin_constraint_0_a1"), lay.max_obstacles, c.params,
+                                      c.guided > 0, hs)
+    np.testing.assert_array_equal(got.view(np.int64), placed.view(np.int64))
+
+
+def test_kernel_cases_cover_what_they_claim():
+    c = rc.kernel_case("C2R-center-warm")
+    K = c.table.knots
+    seg = lambda s, k: int((K[c.path_of[s], 1:c.table.n_segments[c.path_of[s]]] <= c.cur_s[s, k]).sum())  # noqa: E731
+    N = c.lay.N
+    assert len({seg(0, k) for k in range(1, N)}) >= 1 and c.cur_s[1, 1] == K[1, 6]            # on a knot
+    assert len({seg(2, k) for k in range(1, N)}) >= 5                                          # many segments
+    assert seg(3, 1) == 2                                                                      # the last segment
+    assert c.cur_s[4, N - 1] > K[0, 3] and c.cur_s[5, 1] < K[1, 0] and np.isnan(c.cur_s[6, 3])  # past the end, before
+    assert c.table.n_segments.tolist() == [3, 12, 64] and not c.guided[5].any() and c.guided[0].sum() == c.G - 1
+    b = rc.kernel_case("C2R-center-twoway-braking")
+    assert b.main_warm is None and b.cur_s[4, N - 1] > K[0, 3] and (np.diff(b.cur_s, axis=1) >= 0).all()
+    assert rc.kernel_case("JSR-bounds-warm").lay.N == 30
+
+
+def test_placement_guided_rows_after_the_obstacles_non_guided_rows_first():
+    lay = config_layout("C2R")
+    S, G, mo = 3, 4, lay.max_obstacles
+    assert (lay.n_lin, lay.n_ell, mo) == (10, 8, 8)
+    sc = make_scenes(lay, S, G, seed=91)
+    sc.guided[1] = False                                    # a scene with no guided planner
+    p = producers.prepare_host(lay, sc, ROBOT_RADIUS, SETTINGS_WEIGHTS["consistency"], DECELERATION)
+    table = rc.window_table(lay, sc.stage_params)
+    hs = roads.road_halfspaces_host(roads.RoadSettings(2.5, True, R), table, np.arange(S),
+                                    roads.main_spline(sc.state, None, lay.N, lay.dt, DECELERATION))
+    out = roads.apply_road_host(lay, p.params, sc.guided, hs).reshape(S, G, lay.N, lay.npar)
+    base = p.params.reshape(S, G, lay.N, lay.npar)
+    l0 = lay.idx("lin_constraint_0_a1")
+    touched = np.zeros_like(base, bool)
+    for s in range(S):
+        for g in range(G):
+            first = mo if sc.guided[s, g] else 0
+            blk = out[s, g, 1:, l0 + 3 * first:l0 + 3 * first + 6]
+            np.testing.assert_array_equal(blk, hs[s, 1:].reshape(lay.N - 1, 6))
+            touched[s, g, 1:, l0 + 3 * first:l0 + 3 * first + 6] = True
+            if not sc.guided[s, g]:
+                # everything after the road rows stays a dummy (a1 = 1, a2 = 0, b = x + 100)
+                rest = out[s, g, 1:, l0 + 6:l0 + 3 * lay.n_lin].reshape(lay.N - 1, -1, 3)
+                assert (rest[..., 0] == 1.0).all() and (rest[..., 1] == 0.0).all()
+                assert (rest[..., 2] == sc.state[s, 0] + 100.0).all()
+    # stage 0 and every other entry bit-identical to prepare_host's output
+    assert not touched[:, :, 0].any()
+    np.testing.assert_array_equal(out[~touched].view(np.int64), base[~touched].view(np.int64))
+    assert not np.array_equal(out[touched], base[touched])
+
+
+def test_layout_without_the_road_rows_is_rejected():
+    lay = config_layout("C2")
+    sc = make_scenes(lay, 1, 2, seed=3)
+    params = np.zeros((2, lay.N, lay.npar))
+    with pytest.raises(ValueError, match="add_halfspaces"):
+        roads.apply_road_host(lay, params, sc.guided, np.zeros((1, lay.N, 2, 3)))
+    one = tmpc_layout(N=20, max_obstacles=8, add_halfspaces=1)
+    with pytest.raises(ValueError, match="add_halfspaces"):
+        roads.apply_road_host(one, np.zeros((2, 20, one.npar)), sc.guided, np.zeros((1, 20, 2, 3)))
+    with pytest.raises(ValueError):
+        roads.RoadSettings(mode="lanes")
+    with pytest.raises(ValueError, match="bound tables"):
+        roads.road_halfspaces_host(roads.RoadSettings(mode="bounds"), paths.PathTable.from_paths([_straight((0, 0), (9, 0))]),
+                                   [0], np.zeros((1, 21)))
+
+
+def test_road_layouts():
+    for cfg, base, shape in (("C2R", "C2", (20, 10, 8)), ("JSR", "JS", (30, 6, 4))):
+        lay, b = config_layout(cfg), config_layout(base)
+        assert (lay.N, lay.n_lin, lay.n_ell) == shape and lay.max_obstacles == b.max_obstacles
+        assert lay.npar == b.npar + 6 and lay.nh == b.nh + 2
+        assert lay.idx("lin_constraint_%d_b" % (lay.n_lin - 1)) >= 0
+
+
+# ------------------------------------------------------------------ the library (host-only queries)
+
+
+def test_road_shapes_have_builtin_instances():
+    """C2R = Cfg<20, 10, 8, 0, 5, 0> goes LEAN on three lane parts, a storage path no other instance takes"""
+    from oscar_mpc_planner_mr_modification_amd.native_spec import problem_from_layout
+    lib = C.CDLL(os.path.join(PKG, "libmpcg.so"))
+    got = {}
+    for cfg in ("C2R", "JSR"):
+        pr = problem_from_layout(config_layout(cfg))
+        assert lib.mpcg_supported(C.byref(pr)) == 0, cfg
+        buf = C.create_string_buffer(256)
+        assert lib.mpcg_instance_traits(C.byref(pr), buf, 256) == 0, cfg
+        got[cfg] = dict(kv.split("=") for kv in buf.value.decode().split())
+    print(got)
+    assert (got["C2R"]["parts"], got["C2R"]["lean"], got["C2R"]["gfh"]) == ("3", "1", "0")
+    assert (got["JSR"]["parts"], got["JSR"]["lean"], got["JSR"]["fconst"]) == ("2", "1", "1")
+    for t in got.values():
+        assert int(t["lds"]) <= 40 * 1024
+
+
+def test_road_entry_point_is_exported_and_checks_its_arguments():
+    from oscar_mpc_planner_mr_modification_amd import _build
+    from oscar_mpc_planner_mr_modification_amd.native_spec import (ROAD_EXPORTS, MpcgPathTable, MpcgRoadIo,
+                                                                   MpcgRoadSettings, problem_from_layout)
+    lib = C.CDLL(os.path.join(PKG, "libmpcg.so"))
+    for name in ROAD_EXPORTS:
+        assert hasattr(lib, name), name
+    assert _build.ROAD_SOURCES == {"mpcg_road.hip": ["-ffp-contract=off"]}
+    assert "mpcg_road.hip" not in _build.SOURCES and "mpcg_road.h" not in _build.HEADERS
+    assert "mpcg_inst_road.hip" in _build.SOURCES
+    lib.mpcg_last_error.restype = C.c_char_p
+    fn = lib.mpcg_road_halfspaces
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                   C.c_void_p, C.c_void_p]
+    # every rejection happens before a pointer is followed on the device: dummy non-null addresses
+    # (host arrays) stand in for device memory and no launch is reached
+    keep = np.zeros(16)
+    po = np.zeros(1, np.int32)
+    d = keep.ctypes.data
+    tb = MpcgPathTable(d, d, d, d, 1, 4)
+    io = MpcgRoadIo(d, None, 3.0, None, None, None)
+    st = MpcgRoadSettings(6.0, 0.325, 0, 0)
+
+    def call(pr, mo=None, table=tb, sett=st, rio=io, path_of=po, params=d, G=2):
+        lay_mo = 8 if mo is None else mo
+        return fn(C.byref(pr) if pr is not None else None, 1, G, lay_mo, C.byref(sett), C.byref(table),
+                  path_of.ctypes.data if path_of is not None else None, C.byref(rio), params, None, None)
+
+    c2r = problem_from_layout(config_layout("C2R"))
+    assert call(None) == -1
+    assert call(problem_from_layout(config_layout("C2"))) == -1 and b"n_lin >= max_obstacles + 2" in lib.mpcg_last_error()
+    assert call(c2r, mo=9) == -1 and call(c2r, mo=-1) == -1
+    big = problem_from_layout(tmpc_layout(N=33, max_obstacles=4, add_halfspaces=2))
+    assert call(big, mo=4) == -1 and b"N <= 32" in lib.mpcg_last_error()
+    assert call(c2r, table=MpcgPathTable(d, d, d, d, 1, 65)) == -1 and b"M <= 64" in lib.mpcg_last_error()
+    assert call(c2r, table=MpcgPathTable(d, d, d, d, 0, 4)) == -1
+    assert call(c2r, table=MpcgPathTable(None, d, d, d, 1, 4)) == -1
+    assert call(c2r, sett=MpcgRoadSettings(6.0, 0.325, 0, 2)) == -1
+    assert call(c2r, sett=MpcgRoadSettings(6.0, 0.325, 0, 1)) == -1 and b"bound tables" in lib.mpcg_last_error()
+    assert call(c2r, path_of=np.array([1], np.int32)) == -1 and b"outside the table" in lib.mpcg_last_error()
+    assert call(c2r, params=None) == -1 and call(c2r, G=0) == -1
+    assert call(c2r, rio=MpcgRoadIo(None, None, 3.0, None, None, None)) == -1
+    assert call(problem_from_layout(config_layout("C5"))) == -1
