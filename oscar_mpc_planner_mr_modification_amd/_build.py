@@ -21,23 +21,19 @@ SOURCES = {"mpcg_kernels.hip": [], "mpcg_prepare.hip": ["-ffp-contract=off"],
            "mpcg_inst_bicycle.hip": [], "mpcg_inst_road.hip": []}
 HEADERS = ["mpcg_device.h", "mpcg_sqp.h", "mpcg_sqp_body.inc", "mpcg_prepare.h", "mpcg_braking.h", "mpcg_bicycle.h",
            "mpcg_instance.h"]
-# the multi-robot layer (include/mpcg_fleet.h): linked into libmpcg.so but kept out of SOURCES / HEADERS,
-# whose source_hash() is the identity the committed counter profiles (profiles/traffic_*.json) were taken on
-FLEET_SOURCES = {"mpcg_fleet.hip": ["-ffp-contract=off"]}
-FLEET_HEADERS = ["mpcg_fleet.h"]
-# the reference-path tracking (include/mpcg_path.h): linked in the same way, outside source_hash()
-PATH_SOURCES = {"mpcg_path.hip": ["-ffp-contract=off"]}
-PATH_HEADERS = ["mpcg_path.h"]
-# the guidance layer (include/mpcg_guidance.h): linked in the same way, outside source_hash()
-GUIDANCE_SOURCES = {"mpcg_guidance.hip": ["-ffp-contract=off"]}
-GUIDANCE_HEADERS = ["mpcg_guidance.h"]
-# the active-solve compaction (include/mpcg_active.h): linked in the same way, outside source_hash()
-ACTIVE_SOURCES = {"mpcg_active.hip": ["-ffp-contract=off"]}
-ACTIVE_HEADERS = ["mpcg_active.h"]
-# the road-boundary halfspaces (include/mpcg_road.h): linked in the same way, outside source_hash();
-# mpcg_spline.h is the path evaluation it shares with mpcg_path.h
-ROAD_SOURCES = {"mpcg_road.hip": ["-ffp-contract=off"]}
-ROAD_HEADERS = ["mpcg_road.h", "mpcg_spline.h"]
+# the layers around the SQP kernel, by public header under include/ (multi-robot fleet, reference-path
+# tracking, guidance, active-solve compaction, road-boundary halfspaces): linked into libmpcg.so but kept
+# out of SOURCES / HEADERS, whose source_hash() is the identity the committed counter profiles
+# (profiles/traffic_*.json) were taken on.  A new layer is one more row (DESIGN.md "The host-side seam").
+LAYERS = {
+    "mpcg_fleet.h": {"sources": {"mpcg_fleet.hip": ["-ffp-contract=off"]}, "headers": ["mpcg_fleet.h"]},
+    "mpcg_path.h": {"sources": {"mpcg_path.hip": ["-ffp-contract=off"]}, "headers": ["mpcg_path.h"]},
+    "mpcg_guidance.h": {"sources": {"mpcg_guidance.hip": ["-ffp-contract=off"]}, "headers": ["mpcg_guidance.h"]},
+    "mpcg_active.h": {"sources": {"mpcg_active.hip": ["-ffp-contract=off"]}, "headers": ["mpcg_active.h"]},
+    "mpcg_road.h": {"sources": {"mpcg_road.hip": ["-ffp-contract=off"]}, "headers": ["mpcg_road.h"]},
+}
+# csrc headers more than one layer includes: the entry points' checks and error text, the path evaluation
+LAYER_SHARED_HEADERS = ["mpcg_host.h", "mpcg_spline.h"]
 HOST_SOURCES = ["host/mpcg_yaml.cpp", "host/mpcg_solver.cpp"]
 HOST_HEADERS = ["mpc_planner_solver/mpcg_yaml.h", "mpc_planner_solver/mpcg_config.h", "mpc_planner_solver/state.h",
                 "mpc_planner_solver/mpcg_solver_interface.h", "mpc_planner_solver/solver_interface.h"]
@@ -67,16 +63,21 @@ def _stale(target, deps):
     return any(os.path.getmtime(d) > t for d in deps)
 
 
+def lib_sources() -> dict:
+    """every translation unit of libmpcg.so -> its extra flags: SOURCES, then the layers'"""
+    srcs = dict(SOURCES)
+    for layer in LAYERS.values():
+        srcs.update(layer["sources"])
+    return srcs
+
+
 def build_lib(force: bool = False, verbose: bool = False, extra_flags=(), out: str = LIB, sources=None) -> str:
     """libmpcg.so (or a diagnostic / variant build of it with extra_flags at `out`; `sources`
     restricts the built-in instance files of such a build)"""
-    srcs = SOURCES if sources is None else {k: v for k, v in SOURCES.items() if k in sources}
-    srcs = {**srcs, **FLEET_SOURCES, **PATH_SOURCES, **GUIDANCE_SOURCES, **ACTIVE_SOURCES, **ROAD_SOURCES}
-    deps = [os.path.join(CSRC, s) for s in list(SOURCES) + HEADERS + list(FLEET_SOURCES) + FLEET_HEADERS +
-            list(PATH_SOURCES) + PATH_HEADERS + list(GUIDANCE_SOURCES) + GUIDANCE_HEADERS +
-            list(ACTIVE_SOURCES) + ACTIVE_HEADERS + list(ROAD_SOURCES) + ROAD_HEADERS] + \
-        [os.path.join(INCLUDE, h) for h in ("mpcg.h", "mpcg_fleet.h", "mpcg_path.h", "mpcg_guidance.h",
-                                            "mpcg_active.h", "mpcg_road.h")] + [__file__]
+    srcs = {k: v for k, v in lib_sources().items() if sources is None or k not in SOURCES or k in sources}
+    layer_headers = LAYER_SHARED_HEADERS + [h for layer in LAYERS.values() for h in layer["headers"]]
+    deps = [os.path.join(CSRC, f) for f in list(lib_sources()) + HEADERS + layer_headers] + \
+        [os.path.join(INCLUDE, h) for h in ["mpcg.h"] + list(LAYERS)] + [__file__]
     if not force and not _stale(out, deps):
         return out
     objdir = os.path.join(BUILD, "obj" + ("_" + "_".join(f.strip("-").replace("=", "") for f in extra_flags)
@@ -132,53 +133,37 @@ def build_instance(layout, out_dir: str, force: bool = False) -> str:
     return so
 
 
-def build_stage_probe(force: bool = False) -> str:
-    """build/probe/libstage_probe.so: the test-only translation unit tests/cpp/stage_probe.hip
-    (single-thread kernels around the per-stage device functions of mpcg_device.h /
-    mpcg_bicycle.h, tests/test_gpu_stage_functions.py), compiled with the flags of the kernel
-    instances."""
-    src = os.path.join(ROOT, "tests", "cpp", "stage_probe.hip")
+def _build_probe(name: str, headers, force: bool) -> str:
+    """build/probe/lib<name>.so from the test-only translation unit tests/cpp/<name>.hip, which includes
+    `headers` of csrc; compiled with the flags of the kernel instances"""
+    src = os.path.join(ROOT, "tests", "cpp", name + ".hip")
     out_dir = os.path.join(BUILD, "probe")
-    so = os.path.join(out_dir, "libstage_probe.so")
-    deps = [src, os.path.join(INCLUDE, "mpcg.h"), __file__] + [os.path.join(CSRC, h) for h in HEADERS]
+    so = os.path.join(out_dir, f"lib{name}.so")
+    deps = [src, os.path.join(INCLUDE, "mpcg.h"), __file__] + [os.path.join(CSRC, h) for h in headers]
     if force or _stale(so, deps):
         os.makedirs(out_dir, exist_ok=True)
-        obj = _hipcc_obj(src, os.path.join(out_dir, "stage_probe.o"))
+        obj = _hipcc_obj(src, os.path.join(out_dir, name + ".o"))
         subprocess.run(["hipcc", f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", so + ".tmp", obj], check=True)
         os.replace(so + ".tmp", so)
     return so
+
+
+def build_stage_probe(force: bool = False) -> str:
+    """single-thread kernels around the per-stage device functions of mpcg_device.h / mpcg_bicycle.h
+    (tests/test_gpu_stage_functions.py)"""
+    return _build_probe("stage_probe", HEADERS, force)
 
 
 def build_mirror_probe(force: bool = False) -> str:
-    """build/probe/libmirror_probe.so: the test-only translation unit tests/cpp/mirror_probe.hip (one
-    wavefront per workgroup around mirror / mirror_blocks_ok / mirror_stage of mpcg_device.h,
-    tests/test_gpu_mirror_blocks.py), compiled with the flags of the kernel instances."""
-    src = os.path.join(ROOT, "tests", "cpp", "mirror_probe.hip")
-    out_dir = os.path.join(BUILD, "probe")
-    so = os.path.join(out_dir, "libmirror_probe.so")
-    deps = [src, os.path.join(INCLUDE, "mpcg.h"), __file__, os.path.join(CSRC, "mpcg_device.h")]
-    if force or _stale(so, deps):
-        os.makedirs(out_dir, exist_ok=True)
-        obj = _hipcc_obj(src, os.path.join(out_dir, "mirror_probe.o"))
-        subprocess.run(["hipcc", f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", so + ".tmp", obj], check=True)
-        os.replace(so + ".tmp", so)
-    return so
+    """one wavefront per workgroup around mirror / mirror_blocks_ok / mirror_stage of mpcg_device.h
+    (tests/test_gpu_mirror_blocks.py)"""
+    return _build_probe("mirror_probe", ["mpcg_device.h"], force)
 
 
 def build_fac_rows_probe(force: bool = False) -> str:
-    """build/probe/libfac_rows_probe.so: the test-only translation unit tests/cpp/fac_rows_probe.hip (one
-    wavefront around erk_unicycle of mpcg_device.h, one (z, pi) per lane; tests/test_gpu_fac_rows_probe.py),
-    compiled with the flags of the kernel instances."""
-    src = os.path.join(ROOT, "tests", "cpp", "fac_rows_probe.hip")
-    out_dir = os.path.join(BUILD, "probe")
-    so = os.path.join(out_dir, "libfac_rows_probe.so")
-    deps = [src, os.path.join(INCLUDE, "mpcg.h"), __file__, os.path.join(CSRC, "mpcg_device.h")]
-    if force or _stale(so, deps):
-        os.makedirs(out_dir, exist_ok=True)
-        obj = _hipcc_obj(src, os.path.join(out_dir, "fac_rows_probe.o"))
-        subprocess.run(["hipcc", f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", so + ".tmp", obj], check=True)
-        os.replace(so + ".tmp", so)
-    return so
+    """one wavefront around erk_unicycle of mpcg_device.h, one (z, pi) per lane
+    (tests/test_gpu_fac_rows_probe.py)"""
+    return _build_probe("fac_rows_probe", ["mpcg_device.h"], force)
 
 
 # the switch-off builds tests/test_gpu_fac_rows.py compares the production library with (DESIGN.md §3.11):

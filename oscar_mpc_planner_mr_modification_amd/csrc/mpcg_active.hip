@@ -5,10 +5,9 @@
 #include <string>
 
 #include "mpcg_active.h"
+#include "mpcg_host.h"
 
-namespace mpcg {
-extern thread_local std::string g_err;  // defined in mpcg_kernels.hip
-}
+using namespace mpcg::host;
 
 struct mpcg_active_ws {
     int device, max_batch;
@@ -21,25 +20,6 @@ struct mpcg_active_ws {
 };
 
 namespace {
-
-int fail(const char* who, const char* what, int rc = -1) {
-    mpcg::g_err = std::string(who) + ": " + what;
-    return rc;
-}
-
-int hip_fail(const char* who, const char* what, hipError_t e) {
-    mpcg::g_err = std::string(who) + ": " + what + ": " + hipGetErrorString(e);
-    return -1;
-}
-
-int launched(const char* what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        mpcg::g_err = std::string(what) + " launch: " + hipGetErrorString(e);
-        return -1;
-    }
-    return 0;
-}
 
 // block sizes of `pr`; with_qp: whether the QP memory's size is needed (it needs a compiled instance)
 int sizes_of(const char* who, const mpcg_problem* pr, bool with_qp, mpcg::ActiveSizes* z) {

@@ -7,10 +7,9 @@
 #include <string>
 
 #include "mpcg_fleet.h"
+#include "mpcg_host.h"
 
-namespace mpcg {
-extern thread_local std::string g_err;  // defined in mpcg_kernels.hip
-}
+using namespace mpcg::host;
 
 namespace {
 
@@ -18,28 +17,12 @@ namespace {
 int fleet_check(const char* who, const mpcg_problem* pr, int F, int R, int A, const mpcg_fleet_settings* set,
                 const mpcg_fleet_state* st) {
     if (!pr || !set || !st || F < 0 || A < 0 || !st->sent_plan || !st->sent_time || !st->last_send_time ||
-        !st->prev_topology) {
-        mpcg::g_err = std::string(who) + ": invalid arguments";
-        return -1;
-    }
-    if (pr->nx != MPCG_NX) {
-        mpcg::g_err = std::string(who) + ": the fleet layer needs the 5-state model";
-        return -2;
-    }
+        !st->prev_topology)
+        return fail(who, "invalid arguments");
+    if (pr->nx != MPCG_NX) return fail(who, "the fleet layer needs the 5-state model", -2);
     if (pr->N < 2 || pr->N > mpcg::FLEET_MAX_N || pr->n_ell < 0 || pr->n_ell > mpcg::FLEET_MAX_ELL || R < 2 ||
-        R > mpcg::FLEET_MAX_R || A + R - 1 > mpcg::FLEET_MAX_CAND) {
-        mpcg::g_err = std::string(who) + ": needs 2 <= N <= 32, n_ell <= 32, 2 <= R <= 8 and A + R - 1 <= 64";
-        return -2;
-    }
-    return 0;
-}
-
-int launched(const char* what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        mpcg::g_err = std::string(what) + " launch: " + hipGetErrorString(e);
-        return -1;
-    }
+        R > mpcg::FLEET_MAX_R || A + R - 1 > mpcg::FLEET_MAX_CAND)
+        return fail(who, "needs 2 <= N <= 32, n_ell <= 32, 2 <= R <= 8 and A + R - 1 <= 64", -2);
     return 0;
 }
 
@@ -52,10 +35,8 @@ int mpcg_fleet_obstacles(const mpcg_problem* pr, int n_fleets, int n_robots, int
                          const double* array_obst, const double* array_meta, const int* array_id, double now,
                          double* obst, double* obst_meta, void* stream) {
     if (int rc = fleet_check("mpcg_fleet_obstacles", pr, n_fleets, n_robots, n_array, set, st)) return rc;
-    if (!state || (pr->n_ell > 0 && (!obst || !obst_meta)) || (n_array > 0 && (!array_obst || !array_meta))) {
-        mpcg::g_err = "mpcg_fleet_obstacles: invalid arguments";
-        return -1;
-    }
+    if (!state || (pr->n_ell > 0 && (!obst || !obst_meta)) || (n_array > 0 && (!array_obst || !array_meta)))
+        return fail("mpcg_fleet_obstacles", "invalid arguments");
     const int S = n_fleets * n_robots;
     if (S == 0) return 0;
     hipLaunchKernelGGL(mpcg::fleet_shift_kernel, dim3(S), dim3(64), 0, (hipStream_t)stream, S, pr->N, pr->dt, *set,
@@ -73,10 +54,8 @@ int mpcg_fleet_publish(const mpcg_problem* pr, int n_fleets, int n_robots, int n
                        const double* xtraj, const double* state, const int* topology, const unsigned char* guided,
                        double now, int* reason, unsigned char* published, void* stream) {
     if (int rc = fleet_check("mpcg_fleet_publish", pr, n_fleets, n_robots, 0, set, st)) return rc;
-    if (n_guesses < 1 || !best || !xtraj || !state || !reason || !published) {
-        mpcg::g_err = "mpcg_fleet_publish: invalid arguments";
-        return -1;
-    }
+    if (n_guesses < 1 || !best || !xtraj || !state || !reason || !published)
+        return fail("mpcg_fleet_publish", "invalid arguments");
     const int S = n_fleets * n_robots;
     if (S == 0) return 0;
     hipLaunchKernelGGL(mpcg::fleet_publish_kernel, dim3(S), dim3(64), 0, (hipStream_t)stream, S, n_guesses, pr->N,

@@ -7,26 +7,11 @@
 #include <string>
 
 #include "mpcg_guidance.h"
+#include "mpcg_host.h"
 
-namespace mpcg {
-extern thread_local std::string g_err;  // defined in mpcg_kernels.hip
-}
+using namespace mpcg::host;
 
 namespace {
-
-int fail(const char* who, const char* what, int rc = -1) {
-    mpcg::g_err = std::string(who) + ": " + what;
-    return rc;
-}
-
-int launched(const char* what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        mpcg::g_err = std::string(what) + " launch: " + hipGetErrorString(e);
-        return -1;
-    }
-    return 0;
-}
 
 bool null_state(const mpcg_guidance_state* st) {
     return !st || !st->class_traj || !st->class_used || !st->planner_class || !st->selected_topology ||
@@ -57,8 +42,7 @@ int mpcg_guidance_update(const mpcg_problem* pr, int n_scenes, int n_guesses, co
     if (pr->n_seg < 1 || pr->n_seg > MPCG_GUIDANCE_MAX_SEG) return fail(who, "needs 1 <= n_seg <= 8", -2);
     if (n_guesses - 1 < 1 || n_guesses - 1 > MPCG_GUIDANCE_CANDIDATES)
         return fail(who, "needs 1 <= G - 1 <= 8 guided planners", -2);
-    if (pr->i_spline0 < 0 || pr->i_spline0 + 9 * pr->n_seg > pr->npar)
-        return fail(who, "the spline window lies outside the stage parameters");
+    if (int rc = check_spline_window(who, pr)) return rc;  // (nx is 5 here)
     if (n_scenes == 0) return 0;
     hipLaunchKernelGGL(mpcg::guidance_update_kernel, dim3(n_scenes), dim3(64),
                        mpcg::gd_lds_bytes(pr->N, pr->n_ell, pr->n_seg), (hipStream_t)stream, n_scenes,

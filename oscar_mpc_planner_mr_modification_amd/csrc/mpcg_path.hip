@@ -7,28 +7,9 @@
 #include <string>
 
 #include "mpcg_path.h"
+#include "mpcg_host.h"
 
-namespace mpcg {
-extern thread_local std::string g_err;  // defined in mpcg_kernels.hip
-}
-
-namespace {
-
-int fail(const char* who, const char* what) {
-    mpcg::g_err = std::string(who) + ": " + what;
-    return -1;
-}
-
-int launched(const char* what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        mpcg::g_err = std::string(what) + " launch: " + hipGetErrorString(e);
-        return -1;
-    }
-    return 0;
-}
-
-}  // namespace
+using namespace mpcg::host;
 
 extern "C" {
 
@@ -37,19 +18,12 @@ int mpcg_path_update(const mpcg_problem* pr, int n_scenes, const mpcg_path_table
                      unsigned char* reached, void* stream) {
     const char* who = "mpcg_path_update";
     if (!pr || n_scenes < 0) return fail(who, "invalid arguments");
-    if (!tb || !tb->coef || !tb->knots || !tb->n_segments || !tb->path_of) return fail(who, "null path table");
-    if (tb->max_segments < 1 || tb->max_segments > MPCG_PATH_MAX_SEGMENTS)
-        return fail(who, "needs 1 <= M <= 64 segments per path");
-    if (tb->n_paths < 1) return fail(who, "needs at least one path");
+    if (int rc = check_path_table(who, tb)) return rc;
     if (pr->n_seg < 1) return fail(who, "needs n_seg >= 1");
-    if (pr->nx < 2 || pr->i_spline0 < 0 || pr->i_spline0 + 9 * pr->n_seg > pr->npar)
-        return fail(who, "the spline window lies outside the stage parameters");
+    if (int rc = check_spline_window(who, pr)) return rc;
     if (!path_of_host || !state || !closest_segment || !closest_s || !stage_params || !reached)
         return fail(who, "invalid arguments");
-    for (int s = 0; s < n_scenes; ++s)
-        if (path_of_host[s] < 0 || path_of_host[s] >= tb->n_paths)
-            return fail(who, ("path_of[" + std::to_string(s) + "] = " + std::to_string(path_of_host[s]) +
-                              " outside the table").c_str());
+    if (int rc = check_path_of(who, path_of_host, n_scenes, tb->n_paths)) return rc;
     if (n_scenes == 0) return 0;
     hipLaunchKernelGGL(mpcg::path_update_kernel, dim3(n_scenes), dim3(64), 0, (hipStream_t)stream, n_scenes, pr->nx,
                        pr->npar, pr->i_spline0, pr->n_seg, *tb, state, closest_segment, closest_s, stage_params,

@@ -6,19 +6,9 @@
 #include <string>
 
 #include "mpcg_road.h"
+#include "mpcg_host.h"
 
-namespace mpcg {
-extern thread_local std::string g_err;  // defined in mpcg_kernels.hip
-}
-
-namespace {
-
-int fail(const char* who, const char* what) {
-    mpcg::g_err = std::string(who) + ": " + what;
-    return -1;
-}
-
-}  // namespace
+using namespace mpcg::host;
 
 extern "C" {
 
@@ -34,27 +24,16 @@ int mpcg_road_halfspaces(const mpcg_problem* pr, int n_scenes, int n_guesses, in
         return fail(who, "needs n_lin >= max_obstacles + 2 (a solver generated with add_halfspaces 2)");
     if (pr->i_lin0 < 0 || pr->i_lin0 + 3 * pr->n_lin > pr->npar)
         return fail(who, "the lin_constraint block lies outside the stage parameters");
-    if (!tb || !tb->coef || !tb->knots || !tb->n_segments || !tb->path_of) return fail(who, "null path table");
-    if (tb->max_segments < 1 || tb->max_segments > MPCG_PATH_MAX_SEGMENTS)
-        return fail(who, "needs 1 <= M <= 64 segments per path");
-    if (tb->n_paths < 1) return fail(who, "needs at least one path");
+    if (int rc = check_path_table(who, tb)) return rc;
     if (set->mode != MPCG_ROAD_CENTERLINE && set->mode != MPCG_ROAD_BOUNDS) return fail(who, "unknown mode");
     if (set->mode == MPCG_ROAD_BOUNDS && (!io->left_coef || !io->right_coef))
         return fail(who, "the bounds mode needs the left and right bound tables");
     if (!path_of_host || !params || (!io->main_warm && !io->state)) return fail(who, "invalid arguments");
-    for (int s = 0; s < n_scenes; ++s)
-        if (path_of_host[s] < 0 || path_of_host[s] >= tb->n_paths)
-            return fail(who, ("path_of[" + std::to_string(s) + "] = " + std::to_string(path_of_host[s]) +
-                              " outside the table").c_str());
+    if (int rc = check_path_of(who, path_of_host, n_scenes, tb->n_paths)) return rc;
     if (n_scenes == 0) return 0;
     hipLaunchKernelGGL(mpcg::road_halfspaces_kernel, dim3(n_scenes), dim3(64), 0, (hipStream_t)stream, *pr, n_scenes,
                        n_guesses, max_obstacles, *set, *tb, *io, params, halfspaces);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        mpcg::g_err = std::string("road halfspaces launch: ") + hipGetErrorString(e);
-        return -1;
-    }
-    return 0;
+    return launched("road halfspaces");
 }
 
 }  // extern "C"

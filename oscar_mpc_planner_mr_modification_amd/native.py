@@ -9,10 +9,15 @@ import ctypes as C
 import os
 
 import numpy as np
+# Load torch's HIP runtime first: libmpcg.so's libamdhip64.so.7 /
+# libhsa-runtime64.so.1 then resolve (by SONAME) to the copies torch already
+# mapped, so the process holds exactly one HIP runtime and device pointers
+# from torch tensors are valid in our kernels.
+import torch
 
 from .native_spec import (ABI_VERSION, ACTIVE_EXPORTS, DEFAULT_OPTIONS, EXPORTS, FLEET_EXPORTS,  # noqa: F401
                           GUIDANCE_CANDIDATES,
-                          GUIDANCE_EXPORTS, INFO_STRIDE, NU, NVAR, NX, PATH_EXPORTS, STATS_STRIDE, UNICYCLE_LB,
+                          GUIDANCE_EXPORTS, INFO_STRIDE, NU, NVAR, NX, PATH_EXPORTS, SIGNATURES, STATS_STRIDE, UNICYCLE_LB,
                           UNICYCLE_UB, MpcgFleetSettings, MpcgFleetState, MpcgGuidanceOut, MpcgGuidanceSettings,
                           MpcgGuidanceState, MpcgIo, MpcgPathSettings, MpcgPathTable, MpcgProblem, MpcgRoadIo,
                           MpcgRoadSettings, MpcgSceneIo, MpcgStepIo, MpcgScenarioIo, ROAD_EXPORTS, problem_from_layout)
@@ -20,98 +25,18 @@ from .native_spec import (ABI_VERSION, ACTIVE_EXPORTS, DEFAULT_OPTIONS, EXPORTS,
 PKG = os.path.dirname(os.path.abspath(__file__))
 # MPCG_LIB selects a diagnostic build (e.g. libmpcg_stamps.so); default the production library
 LIB_PATH = os.environ.get("MPCG_LIB") or os.path.join(PKG, "libmpcg.so")
+F64, I32, U8 = torch.float64, torch.int32, torch.uint8
+
 
 def _load():
-    # Load torch's HIP runtime first: libmpcg.so's libamdhip64.so.7 /
-    # libhsa-runtime64.so.1 then resolve (by SONAME) to the copies torch already
-    # mapped, so the process holds exactly one HIP runtime and device pointers
-    # from torch tensors are valid in our kernels.
-    import torch  # noqa: F401
-
     if not os.path.exists(LIB_PATH):
         raise ImportError(f"{LIB_PATH} not built: run `python -c 'import __graft_entry__ as g; g.build()'` "
                           "(hipcc --offload-arch=gfx950); there is no CPU fallback")
     lib = C.CDLL(LIB_PATH)
-    P = C.POINTER(MpcgProblem)
-    vp = C.c_void_p
-    lib.mpcg_abi_version.restype = C.c_int
-    lib.mpcg_last_error.restype = C.c_char_p
-    lib.mpcg_supported.argtypes = [P]
-    lib.mpcg_supported.restype = C.c_int
-    lib.mpcg_num_h.argtypes = [P]
-    lib.mpcg_lam_size.argtypes = [P]
-    lib.mpcg_qp_mem_size.argtypes = [P]
-    lib.mpcg_qp_mem_size.restype = C.c_int
-    lib.mpcg_problem_from_map.argtypes = [P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_char_p),
-                                          C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double),
-                                          C.c_double, C.c_int]
-    lib.mpcg_problem_from_map_model.argtypes = [P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                                C.POINTER(C.c_char_p), C.POINTER(C.c_int), C.POINTER(C.c_double),
-                                                C.POINTER(C.c_double), C.c_double, C.c_int]
-    lib.mpcg_solve.argtypes = [P, C.c_int, C.POINTER(MpcgIo), vp]
-    lib.mpcg_solve.restype = C.c_int
-    lib.mpcg_context_create.argtypes = [P, C.c_int]
-    lib.mpcg_context_create.restype = vp
-    lib.mpcg_context_destroy.argtypes = [vp]
-    lib.mpcg_context_solve.argtypes = [vp, C.c_int, C.POINTER(MpcgIo)]
-    lib.mpcg_context_set_iterations.argtypes = [vp, C.c_int]
-    lib.mpcg_solve_batch_device.argtypes = [P, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.mpcg_solve_batch_device.restype = C.c_int
-    lib.mpcg_solve_batch_host.argtypes = [P, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.mpcg_solve_batch_host.restype = C.c_int
-    lib.mpcg_select_best_device.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_double, vp, vp,
-                                            C.c_double, vp, vp, vp, vp]
-    lib.mpcg_select_best_device.restype = C.c_int
-    lib.mpcg_prepare.argtypes = [P, C.c_int, C.c_int, C.POINTER(MpcgSceneIo), vp, vp, vp, vp, vp, vp]
-    lib.mpcg_prepare.restype = C.c_int
-    lib.mpcg_advance.argtypes = [P, C.c_int, C.c_int, C.POINTER(MpcgStepIo), vp, vp, vp, vp, vp, vp, vp]
-    lib.mpcg_advance.restype = C.c_int
-    lib.mpcg_prepare_scenario.argtypes = [P, C.c_int, C.c_int, C.POINTER(MpcgScenarioIo), vp, vp, vp, vp]
-    lib.mpcg_prepare_scenario.restype = C.c_int
-    lib.mpcg_select_lowest_cost_device.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp]
-    lib.mpcg_select_lowest_cost_device.restype = C.c_int
-    lib.mpcg_winner_records_device.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]
-    lib.mpcg_winner_records_device.restype = C.c_int
-    # include/mpcg_fleet.h
-    FS, FT = C.POINTER(MpcgFleetSettings), C.POINTER(MpcgFleetState)
-    lib.mpcg_fleet_obstacles.argtypes = [P, C.c_int, C.c_int, C.c_int, FS, FT, vp, vp, vp, vp, C.c_double, vp, vp, vp]
-    lib.mpcg_fleet_obstacles.restype = C.c_int
-    lib.mpcg_fleet_publish.argtypes = [P, C.c_int, C.c_int, C.c_int, FS, FT, vp, vp, vp, vp, vp, C.c_double, vp, vp, vp]
-    lib.mpcg_fleet_publish.restype = C.c_int
-    # include/mpcg_path.h
-    lib.mpcg_path_update.argtypes = [P, C.c_int, C.POINTER(MpcgPathTable), vp, vp, vp, vp, vp, vp, vp]
-    lib.mpcg_path_update.restype = C.c_int
-    lib.mpcg_path_command.argtypes = [P, C.c_int, C.c_int, C.POINTER(MpcgPathSettings), vp, vp, vp, vp, vp, C.c_int,
-                                      vp, vp, vp]
-    lib.mpcg_path_command.restype = C.c_int
-    # include/mpcg_road.h
-    lib.mpcg_road_halfspaces.argtypes = [P, C.c_int, C.c_int, C.c_int, C.POINTER(MpcgRoadSettings),
-                                         C.POINTER(MpcgPathTable), vp, C.POINTER(MpcgRoadIo), vp, vp, vp]
-    lib.mpcg_road_halfspaces.restype = C.c_int
-    # include/mpcg_guidance.h
-    lib.mpcg_guidance_update.argtypes = [P, C.c_int, C.c_int, C.POINTER(MpcgGuidanceSettings), vp, vp, vp, vp,
-                                         C.POINTER(MpcgGuidanceState), C.POINTER(MpcgGuidanceOut), vp]
-    lib.mpcg_guidance_update.restype = C.c_int
-    lib.mpcg_guidance_mask.argtypes = [C.c_int, C.c_int, vp, vp, vp]
-    lib.mpcg_guidance_mask.restype = C.c_int
-    lib.mpcg_guidance_select.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, C.POINTER(MpcgGuidanceState), vp]
-    lib.mpcg_guidance_select.restype = C.c_int
-    # include/mpcg_active.h
-    IO = C.POINTER(MpcgIo)
-    lib.mpcg_active_plan.argtypes = [C.c_int, vp, vp, vp, vp, vp]
-    lib.mpcg_active_plan.restype = C.c_int
-    lib.mpcg_active_gather.argtypes = [P, C.c_int, vp, IO, IO, vp]
-    lib.mpcg_active_gather.restype = C.c_int
-    lib.mpcg_active_scatter.argtypes = [P, C.c_int, vp, IO, IO, vp]
-    lib.mpcg_active_scatter.restype = C.c_int
-    lib.mpcg_active_ws_create.argtypes = [P, C.c_int, C.c_int, C.c_int, C.c_int]
-    lib.mpcg_active_ws_create.restype = vp
-    lib.mpcg_active_ws_destroy.argtypes = [vp]
-    lib.mpcg_active_ws_destroy.restype = None
-    lib.mpcg_active_ws_read_plan.argtypes = [vp, C.c_int, vp, vp, vp]
-    lib.mpcg_active_ws_read_plan.restype = C.c_int
-    lib.mpcg_solve_active.argtypes = [P, C.c_int, IO, vp, vp, C.POINTER(C.c_int), vp]
-    lib.mpcg_solve_active.restype = C.c_int
+    for group in SIGNATURES.values():
+        for name, (restype, argtypes) in group.items():
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = restype, argtypes
     # (MPCG_ABI_ACCEPT_OLDER, A/B timing runs of an earlier round's library only: ABI versions whose
     # mpcg_problem is a prefix of this one -- later ABIs only append fields)
     older = {int(v) for v in os.environ.get("MPCG_ABI_ACCEPT_OLDER", "").split(",") if v.strip().isdigit()}
@@ -150,6 +75,23 @@ def _ptr(t):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+def _addr(t):
+    return None if t is None else t.data_ptr()
+
+
+def _stream(stream, dev):
+    """the hipStream_t of `stream` (a torch.cuda stream), or of the current stream of `dev` when it is None"""
+    return C.c_void_p((stream if stream is not None else torch.cuda.current_stream(dev)).cuda_stream)
+
+
+def _dev(name, t, dtype, size=None):
+    """assert that `t` is a contiguous device tensor of `dtype`, of the shape `size` (a tuple) or of `size`
+    elements (an int)"""
+    assert t.dtype == dtype and t.is_cuda and t.is_contiguous(), (name, t.dtype, t.device)
+    if size is not None:
+        assert (t.numel() == size if isinstance(size, int) else tuple(t.shape) == size), (name, tuple(t.shape), size)
+
+
 def _check(rc, what):
     if rc != 0:
         raise RuntimeError(f"{what} failed ({rc}): {last_error()}")
@@ -168,6 +110,40 @@ def qp_mem_size(pr: MpcgProblem) -> int:
     return n
 
 
+def _solve_outputs(pr: MpcgProblem, B: int, dev, out, lam_out, qp_out, stats) -> dict:
+    """solve_batch_device's result dict: `out`, or a new one when it is None, with the optional blocks that
+    are asked for allocated where it lacks them (a dict that is passed in is not checked)"""
+    N, nx = pr.N, pr.nx
+    new = lambda dtype, *shape: torch.empty(shape, dtype=dtype, device=dev)  # noqa: E731
+    if out is None:
+        out = dict(xtraj=new(F64, B, N + 1, nx), utraj=new(F64, B, N, pr.nu), pobj=new(F64, B), exit=new(I32, B),
+                   info=new(I32, B, INFO_STRIDE))
+    if lam_out and "lam" not in out:
+        out["lam"] = new(F64, B, N, lam_stride(pr))
+    if qp_out and "qp" not in out:
+        out["qp"] = new(F64, B, qp_mem_size(pr))
+    if stats and "stats" not in out:
+        out["stats"] = new(F64, B, STATS_STRIDE)
+    return out
+
+
+def _solve_io(pr: MpcgProblem, params, warm, xinit, lam_in, qp_in, out: dict, lam_out, qp_out, stats) -> MpcgIo:
+    """The mpcg_io of a solve of params.shape[0] problems: the inputs, checked, and the blocks of `out`
+    (_solve_outputs) that the call asks for."""
+    B, N, nx = params.shape[0], pr.N, pr.nx
+    _dev("params", params, F64, (B, N, pr.npar))
+    _dev("warm", warm, F64, (B, N + 1, pr.nu + nx))
+    _dev("xinit", xinit, F64, (B, nx))
+    if lam_in is not None:
+        _dev("lam_in", lam_in, F64, (B, N, lam_stride(pr)))
+    if qp_in is not None:
+        _dev("qp_in", qp_in, F64, (B, qp_mem_size(pr)))
+    return MpcgIo(params.data_ptr(), warm.data_ptr(), xinit.data_ptr(), _addr(lam_in),
+                  out["xtraj"].data_ptr(), out["utraj"].data_ptr(), out["pobj"].data_ptr(), out["exit"].data_ptr(),
+                  _addr(out.get("info")), out["lam"].data_ptr() if lam_out else None, _addr(qp_in),
+                  out["qp"].data_ptr() if qp_out else None, out["stats"].data_ptr() if stats else None)
+
+
 def solve_batch_device(pr: MpcgProblem, params, warm, xinit, out=None, stream=None, lam_in=None,
                        lam_out=False, qp_in=None, qp_out=False, stats=False):
     """Batched solve on device tensors (torch, float64, on the current HIP device).
@@ -176,45 +152,22 @@ def solve_batch_device(pr: MpcgProblem, params, warm, xinit, out=None, stream=No
     over from the previous solve.  Returns a dict of device tensors (+ "lam" if
     lam_out, "qp" if qp_out, "stats" (B, 4) NLP residuals if stats);
     asynchronous on `stream` (torch.cuda stream or None = current)."""
-    import torch
-
-    B = params.shape[0]
-    N, nx, NU = pr.N, pr.nx, pr.nu
-    LS = lam_stride(pr)
-    assert params.dtype == torch.float64 and params.is_cuda and params.is_contiguous()
-    assert tuple(params.shape) == (B, N, pr.npar), (tuple(params.shape), (B, N, pr.npar))
-    assert tuple(warm.shape) == (B, N + 1, NU + nx) and warm.is_contiguous() and warm.dtype == torch.float64
-    assert tuple(xinit.shape) == (B, nx) and xinit.is_contiguous() and xinit.dtype == torch.float64
-    if lam_in is not None:
-        assert tuple(lam_in.shape) == (B, N, LS) and lam_in.is_contiguous() and lam_in.dtype == torch.float64
-    dev = params.device
-    if out is None:
-        out = dict(xtraj=torch.empty((B, N + 1, nx), dtype=torch.float64, device=dev),
-                   utraj=torch.empty((B, N, NU), dtype=torch.float64, device=dev),
-                   pobj=torch.empty((B,), dtype=torch.float64, device=dev),
-                   exit=torch.empty((B,), dtype=torch.int32, device=dev),
-                   info=torch.empty((B, INFO_STRIDE), dtype=torch.int32, device=dev))
-    if lam_out and "lam" not in out:
-        out["lam"] = torch.empty((B, N, LS), dtype=torch.float64, device=dev)
-    Q = qp_mem_size(pr) if (qp_in is not None or qp_out) else 0
-    if qp_in is not None:
-        assert tuple(qp_in.shape) == (B, Q) and qp_in.is_contiguous() and qp_in.dtype == torch.float64
-    if qp_out and "qp" not in out:
-        out["qp"] = torch.empty((B, Q), dtype=torch.float64, device=dev)
-    if stats and "stats" not in out:
-        out["stats"] = torch.empty((B, STATS_STRIDE), dtype=torch.float64, device=dev)
-    s = stream if stream is not None else torch.cuda.current_stream(dev)
-    io = MpcgIo(params.data_ptr(), warm.data_ptr(), xinit.data_ptr(),
-                None if lam_in is None else lam_in.data_ptr(),
-                out["xtraj"].data_ptr(), out["utraj"].data_ptr(), out["pobj"].data_ptr(), out["exit"].data_ptr(),
-                out["info"].data_ptr() if out.get("info") is not None else None,
-                out["lam"].data_ptr() if lam_out else None,
-                None if qp_in is None else qp_in.data_ptr(),
-                out["qp"].data_ptr() if qp_out else None,
-                out["stats"].data_ptr() if stats else None)
-    rc = lib.mpcg_solve(C.byref(pr), B, C.byref(io), C.c_void_p(s.cuda_stream))
-    _check(rc, "mpcg_solve")
+    B, dev = params.shape[0], params.device
+    out = _solve_outputs(pr, B, dev, out, lam_out, qp_out, stats)
+    io = _solve_io(pr, params, warm, xinit, lam_in, qp_in, out, lam_out, qp_out, stats)
+    _check(lib.mpcg_solve(C.byref(pr), B, C.byref(io), _stream(stream, dev)), "mpcg_solve")
     return out
+
+
+def _host_arrays(pr: MpcgProblem, params, warm, xinit):
+    """The inputs of a host-buffer solve as contiguous float64 arrays, their shapes checked, and its zeroed
+    result dict: (B, params, warm, xinit, result)."""
+    params, warm, xinit = (np.ascontiguousarray(a, np.float64) for a in (params, warm, xinit))
+    B, N, nx, nu = params.shape[0], pr.N, pr.nx, pr.nu
+    assert params.shape == (B, N, pr.npar) and warm.shape == (B, N + 1, nu + nx) and xinit.shape == (B, nx)
+    r = dict(xtraj=np.zeros((B, N + 1, nx)), utraj=np.zeros((B, N, nu)), pobj=np.zeros(B),
+             exit=np.zeros(B, np.int32), info=np.zeros((B, INFO_STRIDE), np.int32))
+    return B, params, warm, xinit, r
 
 
 class Context:
@@ -244,14 +197,8 @@ class Context:
 
     def solve(self, params, warm, xinit, lam_in=None, lam_out=False, qp_in=None, qp_out=False, stats=False):
         pr = self.pr
-        B, N, nx, NU = params.shape[0], pr.N, pr.nx, pr.nu
-        LS = lam_stride(pr)
-        params = np.ascontiguousarray(params, np.float64)
-        warm = np.ascontiguousarray(warm, np.float64)
-        xinit = np.ascontiguousarray(xinit, np.float64)
-        assert params.shape == (B, N, pr.npar) and warm.shape == (B, N + 1, NU + nx) and xinit.shape == (B, nx)
-        r = dict(xtraj=np.zeros((B, N + 1, nx)), utraj=np.zeros((B, N, NU)), pobj=np.zeros(B),
-                 exit=np.zeros(B, np.int32), info=np.zeros((B, INFO_STRIDE), np.int32))
+        B, params, warm, xinit, r = _host_arrays(pr, params, warm, xinit)
+        N, LS = pr.N, lam_stride(pr)
         if lam_in is not None:
             lam_in = np.ascontiguousarray(lam_in, np.float64)
             assert lam_in.shape == (B, N, LS)
@@ -273,22 +220,12 @@ class Context:
 
 def solve_batch_host(pr: MpcgProblem, params: np.ndarray, warm: np.ndarray, xinit: np.ndarray):
     """Host-buffer solve through the same kernels (copies in/out, synchronous)."""
-    B = params.shape[0]
-    N, nx, NU = pr.N, pr.nx, pr.nu
-    params = np.ascontiguousarray(params, np.float64)
-    warm = np.ascontiguousarray(warm, np.float64)
-    xinit = np.ascontiguousarray(xinit, np.float64)
-    assert params.shape == (B, N, pr.npar) and warm.shape == (B, N + 1, NU + nx) and xinit.shape == (B, nx)
-    xt = np.zeros((B, N + 1, nx))
-    ut = np.zeros((B, N, NU))
-    po = np.zeros(B)
-    ex = np.zeros(B, np.int32)
-    info = np.zeros((B, INFO_STRIDE), np.int32)
+    B, params, warm, xinit, r = _host_arrays(pr, params, warm, xinit)
     vp = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
-    rc = lib.mpcg_solve_batch_host(C.byref(pr), B, vp(params), vp(warm), vp(xinit), vp(xt), vp(ut), vp(po),
-                                   vp(ex), vp(info))
+    rc = lib.mpcg_solve_batch_host(C.byref(pr), B, vp(params), vp(warm), vp(xinit), vp(r["xtraj"]), vp(r["utraj"]),
+                                   vp(r["pobj"]), vp(r["exit"]), vp(r["info"]))
     _check(rc, "mpcg_solve_batch_host")
-    return dict(xtraj=xt, utraj=ut, pobj=po, exit=ex, info=info)
+    return r
 
 
 def select_best_device(n_scenes, n_guesses, N, xtraj, pobj, exit_code, prev_traj=None, w_cons=0.0,
@@ -296,16 +233,13 @@ def select_best_device(n_scenes, n_guesses, N, xtraj, pobj, exit_code, prev_traj
                        disabled=None, stream=None, with_objective: bool = True):
     """mpcg_select_best_device -> (best, objective); with_objective=False passes no objective
     buffer (NULL) and returns (best, None)."""
-    import torch
-
     dev = pobj.device
-    best = torch.empty((n_scenes,), dtype=torch.int32, device=dev)
-    objective = torch.empty((n_scenes * n_guesses,), dtype=torch.float64, device=dev) if with_objective else None
-    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    best = torch.empty((n_scenes,), dtype=I32, device=dev)
+    objective = torch.empty((n_scenes * n_guesses,), dtype=F64, device=dev) if with_objective else None
     rc = lib.mpcg_select_best_device(n_scenes, n_guesses, N, _ptr(xtraj), _ptr(pobj), _ptr(exit_code),
                                      _ptr(prev_traj), float(w_cons), _ptr(consistency_enabled),
                                      _ptr(previously_selected), float(selection_weight), _ptr(disabled),
-                                     _ptr(best), _ptr(objective), C.c_void_p(s.cuda_stream))
+                                     _ptr(best), _ptr(objective), _stream(stream, dev))
     _check(rc, "mpcg_select_best_device")
     return best, objective
 
@@ -313,35 +247,30 @@ def select_best_device(n_scenes, n_guesses, N, xtraj, pobj, exit_code, prev_traj
 def winner_records_device(xtraj, utraj, pobj, best, n_guesses, out, stream=None):
     """mpcg_winner_records_device: the selected planner's record per scene (one launch; the device
     form of distributed.winner_records) into `out` [n_scenes][winner_width]."""
-    import torch
-
     n_scenes = best.shape[0]
     B, N1, nx = xtraj.shape
     nu = utraj.shape[2]
     assert B == n_scenes * n_guesses and out.shape[0] == n_scenes and out.shape[1] == N1 * nx + (N1 - 1) * nu + 2
-    for t in (xtraj, utraj, pobj, out):
-        assert t.dtype == torch.float64 and t.is_contiguous()
-    assert best.dtype == torch.int32 and best.is_contiguous()
-    s = stream if stream is not None else torch.cuda.current_stream(pobj.device)
+    for k, t in dict(xtraj=xtraj, utraj=utraj, pobj=pobj, out=out).items():
+        _dev(k, t, F64)
+    _dev("best", best, I32)
     rc = lib.mpcg_winner_records_device(n_scenes, n_guesses, N1 - 1, nx, nu, _ptr(xtraj), _ptr(utraj), _ptr(pobj),
-                                        _ptr(best), _ptr(out), C.c_void_p(s.cuda_stream))
+                                        _ptr(best), _ptr(out), _stream(stream, pobj.device))
     _check(rc, "mpcg_winner_records_device")
     return out
 
 
 def scenes_to_device(scenes, device):
     """producers.Scenes -> dict of contiguous device tensors (float64 / uint8)."""
-    import torch
-
-    def t(a, dt=torch.float64):
+    def t(a, dt=F64):
         return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(device=device, dtype=dt)
 
     return dict(stage_params=t(scenes.stage_params), state=t(scenes.state), obst=t(scenes.obst),
                 obst_meta=t(scenes.obst_meta), guidance=t(scenes.guidance),
-                guided=t(scenes.guided.astype(np.uint8), torch.uint8), main_warm=t(scenes.main_warm),
+                guided=t(scenes.guided.astype(np.uint8), U8), main_warm=t(scenes.main_warm),
                 prev_traj=t(scenes.prev_traj), prev_elapsed=t(scenes.prev_elapsed),
-                consistency_on=t(scenes.consistency_on.astype(np.uint8), torch.uint8),
-                previously_selected=t(scenes.previously_selected.astype(np.uint8), torch.uint8),
+                consistency_on=t(scenes.consistency_on.astype(np.uint8), U8),
+                previously_selected=t(scenes.previously_selected.astype(np.uint8), U8),
                 n_scenes=scenes.n_scenes, n_guesses=scenes.n_guesses)
 
 
@@ -353,27 +282,24 @@ def prepare_device(pr: MpcgProblem, dsc: dict, robot_radius: float, w_consistenc
     warmstart_with_mpc_solution: guided planners whose dsc["existing_guidance"] is set start
     from their own previous output dsc["planner_xtraj"] / ["planner_utraj"]
     (guidance_constraints.cpp:335-338)."""
-    import torch
-
     S, G, N = dsc["n_scenes"], dsc["n_guesses"], pr.N
     dev = dsc["state"].device
     assert tuple(dsc["stage_params"].shape) == (S, pr.npar)
     assert tuple(dsc["obst"].shape) == (S, pr.n_ell, N, 5) and tuple(dsc["guidance"].shape) == (S, G, N + 1, 4)
     if out is None:
-        out = dict(params=torch.empty((S * G, N, pr.npar), dtype=torch.float64, device=dev),
-                   warm=torch.empty((S * G, N + 1, NVAR), dtype=torch.float64, device=dev),
-                   xinit=torch.empty((S * G, NX), dtype=torch.float64, device=dev),
-                   prev_interp=torch.empty((S, N, 2), dtype=torch.float64, device=dev),
-                   consistency_active=torch.empty((S * G,), dtype=torch.uint8, device=dev))
-    p = lambda k: None if dsc.get(k) is None else dsc[k].data_ptr()  # noqa: E731
+        out = dict(params=torch.empty((S * G, N, pr.npar), dtype=F64, device=dev),
+                   warm=torch.empty((S * G, N + 1, NVAR), dtype=F64, device=dev),
+                   xinit=torch.empty((S * G, NX), dtype=F64, device=dev),
+                   prev_interp=torch.empty((S, N, 2), dtype=F64, device=dev),
+                   consistency_active=torch.empty((S * G,), dtype=U8, device=dev))
+    p = lambda k: _addr(dsc.get(k))  # noqa: E731
     sio = MpcgSceneIo(p("stage_params"), p("state"), p("obst"), p("obst_meta"), p("guidance"), p("guided"),
                       p("main_warm"), p("prev_traj"), p("prev_elapsed"), p("consistency_on"),
                       float(robot_radius), float(w_consistency), float(deceleration),
                       p("planner_xtraj"), p("planner_utraj"), p("existing_guidance"),
                       int(bool(warmstart_with_mpc_solution)), int(bool(shift_forward)))
-    s = stream if stream is not None else torch.cuda.current_stream(dev)
     rc = lib.mpcg_prepare(C.byref(pr), S, G, C.byref(sio), _ptr(out["params"]), _ptr(out["warm"]), _ptr(out["xinit"]),
-                          _ptr(out["prev_interp"]), _ptr(out["consistency_active"]), C.c_void_p(s.cuda_stream))
+                          _ptr(out["prev_interp"]), _ptr(out["consistency_active"]), _stream(stream, dev))
     _check(rc, "mpcg_prepare")
     return out
 
@@ -386,38 +312,29 @@ def advance_device(pr: MpcgProblem, S: int, G: int, best, exit_code, xtraj, utra
     out: preallocated dict(main_warm, prev_traj, prev_elapsed, consistency_on, previously_selected,
     lam) to write into; its lam may be None (no multipliers carried) or a tensor also when lam_out
     is None (the kernel then writes zeros)."""
-    import torch
-
     dev = xtraj.device
     N = pr.N
-    LS = lam_stride(pr)
+    shapes = dict(main_warm=(S, N + 1, NVAR), prev_traj=(S, N, 2), prev_elapsed=(S,), consistency_on=(S, G),
+                  previously_selected=(S, G), lam=(S * G, N, lam_stride(pr)))
+    dtypes = dict(consistency_on=U8, previously_selected=U8)
     if out is None:
-        out = dict(main_warm=torch.empty((S, N + 1, NVAR), dtype=torch.float64, device=dev),
-                   prev_traj=torch.empty((S, N, 2), dtype=torch.float64, device=dev),
-                   prev_elapsed=torch.empty((S,), dtype=torch.float64, device=dev),
-                   consistency_on=torch.empty((S, G), dtype=torch.uint8, device=dev),
-                   previously_selected=torch.empty((S, G), dtype=torch.uint8, device=dev),
-                   lam=None if lam_out is None else torch.empty((S * G, N, LS), dtype=torch.float64, device=dev))
+        out = {k: torch.empty(shp, dtype=dtypes.get(k, F64), device=dev) for k, shp in shapes.items()
+               if k != "lam" or lam_out is not None}
+        out.setdefault("lam", None)
     else:
-        shapes = dict(main_warm=(S, N + 1, NVAR), prev_traj=(S, N, 2), prev_elapsed=(S,), consistency_on=(S, G),
-                      previously_selected=(S, G), lam=(S * G, N, LS))
         for k, shp in shapes.items():
-            t = out[k]
-            if t is None and k == "lam":
+            if k == "lam" and out[k] is None:
                 continue
-            want = torch.uint8 if k in ("consistency_on", "previously_selected") else torch.float64
-            assert tuple(t.shape) == shp and t.dtype == want and t.is_contiguous() and t.device == dev, k
-    best32 = best.to(torch.int32).contiguous()
+            _dev(k, out[k], dtypes.get(k, F64), shp)
+            assert out[k].device == dev, k
+    best32 = best.to(I32).contiguous()
     sio = MpcgStepIo(best32.data_ptr(), exit_code.data_ptr(), xtraj.data_ptr(), utraj.data_ptr(), warm.data_ptr(),
-                     None if lam_out is None else lam_out.data_ptr(), state_next.data_ptr(), guided.data_ptr(),
-                     None if topology is None else topology.data_ptr(),
-                     None if topology_next is None else topology_next.data_ptr(),
-                     None if previously_selected is None else previously_selected.data_ptr(),
-                     int(shift_forward), int(consistency_on_non_guided), float(elapsed), float(deceleration))
-    s = stream if stream is not None else torch.cuda.current_stream(dev)
+                     _addr(lam_out), state_next.data_ptr(), guided.data_ptr(), _addr(topology), _addr(topology_next),
+                     _addr(previously_selected), int(shift_forward), int(consistency_on_non_guided), float(elapsed),
+                     float(deceleration))
     rc = lib.mpcg_advance(C.byref(pr), S, G, C.byref(sio), _ptr(out["main_warm"]), _ptr(out["prev_traj"]),
                           _ptr(out["prev_elapsed"]), _ptr(out["consistency_on"]), _ptr(out["previously_selected"]),
-                          _ptr(out["lam"]), C.c_void_p(s.cuda_stream))
+                          _ptr(out["lam"]), _stream(stream, dev))
     _check(rc, "mpcg_advance")
     return out
 
@@ -427,50 +344,43 @@ def prepare_scenario_device(pr: MpcgProblem, n_solvers: int, stage_params, state
     """SH-MPC solver inputs on the GPU (mpcg_prepare_scenario): stage_params
     (S, npar), state (S, nx), samples (S*P, N, M, 2), optional main_warm
     (S, N+1, nu+nx) -> dict(params, warm, xinit) device tensors."""
-    import torch
-
     S = stage_params.shape[0]
     N, nx = pr.N, pr.nx
     B = S * n_solvers
-    for t in (stage_params, state, samples) + (() if main_warm is None else (main_warm,)):
-        assert t.dtype == torch.float64 and t.is_cuda and t.is_contiguous()
-    assert tuple(state.shape) == (S, nx) and stage_params.shape[1] == pr.npar
+    _dev("stage_params", stage_params, F64)
+    _dev("state", state, F64, (S, nx))
+    _dev("samples", samples, F64)
+    if main_warm is not None:
+        _dev("main_warm", main_warm, F64)
+    assert stage_params.shape[1] == pr.npar
     assert samples.shape[0] == B and samples.shape[1] == N and samples.shape[3] == 2
     dev = stage_params.device
     if out is None:
-        out = dict(params=torch.empty((B, N, pr.npar), dtype=torch.float64, device=dev),
-                   warm=torch.empty((B, N + 1, NU + nx), dtype=torch.float64, device=dev),
-                   xinit=torch.empty((B, nx), dtype=torch.float64, device=dev))
-    io = MpcgScenarioIo(stage_params.data_ptr(), state.data_ptr(),
-                        None if main_warm is None else main_warm.data_ptr(), samples.data_ptr(),
+        out = dict(params=torch.empty((B, N, pr.npar), dtype=F64, device=dev),
+                   warm=torch.empty((B, N + 1, NU + nx), dtype=F64, device=dev),
+                   xinit=torch.empty((B, nx), dtype=F64, device=dev))
+    io = MpcgScenarioIo(stage_params.data_ptr(), state.data_ptr(), _addr(main_warm), samples.data_ptr(),
                         int(samples.shape[2]), float(radius), float(deceleration))
-    s = stream if stream is not None else torch.cuda.current_stream(dev)
     rc = lib.mpcg_prepare_scenario(C.byref(pr), S, n_solvers, C.byref(io), _ptr(out["params"]), _ptr(out["warm"]),
-                                   _ptr(out["xinit"]), C.c_void_p(s.cuda_stream))
+                                   _ptr(out["xinit"]), _stream(stream, dev))
     _check(rc, "mpcg_prepare_scenario")
     return out
 
 
 def select_lowest_cost_device(n_scenes, n_solvers, pobj, exit_code, out=None, stream=None):
-    import torch
-
     dev = pobj.device
-    best = out if out is not None else torch.empty((n_scenes,), dtype=torch.int32, device=dev)
-    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    best = out if out is not None else torch.empty((n_scenes,), dtype=I32, device=dev)
     rc = lib.mpcg_select_lowest_cost_device(n_scenes, n_solvers, _ptr(pobj), _ptr(exit_code), _ptr(best),
-                                            C.c_void_p(s.cuda_stream))
+                                            _stream(stream, dev))
     _check(rc, "mpcg_select_lowest_cost_device")
     return best
 
 
 def _fleet_state(fstate: dict, S: int, N: int) -> MpcgFleetState:
-    import torch
-
-    sp, stm, lst, pt = (fstate[k] for k in ("sent_plan", "sent_time", "last_send_time", "prev_topology"))
-    for t_, n in ((sp, S * N * 3), (stm, S), (lst, S)):
-        assert t_.dtype == torch.float64 and t_.is_cuda and t_.is_contiguous() and t_.numel() == n
-    assert pt.dtype == torch.int32 and pt.is_cuda and pt.is_contiguous() and pt.numel() == S
-    return MpcgFleetState(sp.data_ptr(), stm.data_ptr(), lst.data_ptr(), pt.data_ptr())
+    sizes = dict(sent_plan=S * N * 3, sent_time=S, last_send_time=S, prev_topology=S)
+    for k, n in sizes.items():
+        _dev(k, fstate[k], I32 if k == "prev_topology" else F64, n)
+    return MpcgFleetState(*(fstate[k].data_ptr() for k in sizes))
 
 
 def fleet_obstacles_device(pr: MpcgProblem, F: int, R: int, settings: MpcgFleetSettings, fstate: dict, state, now: float,
@@ -481,26 +391,21 @@ def fleet_obstacles_device(pr: MpcgProblem, F: int, R: int, settings: MpcgFleetS
     obst (S, n_ell, N, 5) / obst_meta (S, n_ell, 2), S = F * R.  array_obst (F, A, N, 5), array_meta
     (F, A, 2), array_id (F, A) int32 or None: the fleets' non-communicating obstacles.
     Asynchronous on `stream`; nothing is allocated."""
-    import torch
-
     S, N = F * R, pr.N
     A = 0 if array_obst is None else array_obst.shape[1]
-    assert tuple(state.shape) == (S, pr.nx) and state.dtype == torch.float64 and state.is_contiguous()
-    assert tuple(obst.shape) == (S, pr.n_ell, N, 5) and tuple(obst_meta.shape) == (S, pr.n_ell, 2)
-    for t_ in (obst, obst_meta):
-        assert t_.dtype == torch.float64 and t_.is_cuda and t_.is_contiguous()
+    _dev("state", state, F64, (S, pr.nx))
+    _dev("obst", obst, F64, (S, pr.n_ell, N, 5))
+    _dev("obst_meta", obst_meta, F64, (S, pr.n_ell, 2))
     if A:
-        assert tuple(array_obst.shape) == (F, A, N, 5) and tuple(array_meta.shape) == (F, A, 2)
-        for t_ in (array_obst, array_meta):
-            assert t_.dtype == torch.float64 and t_.is_cuda and t_.is_contiguous()
+        _dev("array_obst", array_obst, F64, (F, A, N, 5))
+        _dev("array_meta", array_meta, F64, (F, A, 2))
         if array_id is not None:
-            assert tuple(array_id.shape) == (F, A) and array_id.dtype == torch.int32 and array_id.is_contiguous()
+            _dev("array_id", array_id, I32, (F, A))
     st = _fleet_state(fstate, S, N)
-    s = stream if stream is not None else torch.cuda.current_stream(state.device)
     rc = lib.mpcg_fleet_obstacles(C.byref(pr), F, R, A, C.byref(settings), C.byref(st), _ptr(state),
                                   _ptr(array_obst) if A else None, _ptr(array_meta) if A else None,
                                   _ptr(array_id) if A else None, float(now), _ptr(obst), _ptr(obst_meta),
-                                  C.c_void_p(s.cuda_stream))
+                                  _stream(stream, state.device))
     _check(rc, "mpcg_fleet_obstacles")
 
 
@@ -511,31 +416,26 @@ def fleet_publish_device(pr: MpcgProblem, F: int, R: int, G: int, settings: Mpcg
     `fstate` in place.  best (S,) int32, xtraj (S*G, N+1, nx), state (S, nx), topology (S, G) int32
     or None, guided (S, G) uint8 or None; outputs reason (S,) int32, published (S,) uint8.
     Asynchronous on `stream`; nothing is allocated."""
-    import torch
-
     S, N = F * R, pr.N
-    assert best.dtype == torch.int32 and best.is_contiguous() and best.numel() == S
-    assert tuple(xtraj.shape) == (S * G, N + 1, pr.nx) and xtraj.dtype == torch.float64 and xtraj.is_contiguous()
-    assert tuple(state.shape) == (S, pr.nx) and state.dtype == torch.float64 and state.is_contiguous()
-    assert reason.dtype == torch.int32 and reason.is_contiguous() and reason.numel() == S
-    assert published.dtype == torch.uint8 and published.is_contiguous() and published.numel() == S
+    _dev("best", best, I32, S)
+    _dev("xtraj", xtraj, F64, (S * G, N + 1, pr.nx))
+    _dev("state", state, F64, (S, pr.nx))
+    _dev("reason", reason, I32, S)
+    _dev("published", published, U8, S)
     if topology is not None:
-        assert topology.dtype == torch.int32 and topology.is_contiguous() and topology.numel() == S * G
+        _dev("topology", topology, I32, S * G)
     if guided is not None:
-        assert guided.dtype == torch.uint8 and guided.is_contiguous() and guided.numel() == S * G
+        _dev("guided", guided, U8, S * G)
     st = _fleet_state(fstate, S, N)
-    s = stream if stream is not None else torch.cuda.current_stream(state.device)
     rc = lib.mpcg_fleet_publish(C.byref(pr), F, R, G, C.byref(settings), C.byref(st), _ptr(best), _ptr(xtraj),
                                 _ptr(state), _ptr(topology), _ptr(guided), float(now), _ptr(reason), _ptr(published),
-                                C.c_void_p(s.cuda_stream))
+                                _stream(stream, state.device))
     _check(rc, "mpcg_fleet_publish")
 
 
 def path_table_device(table, path_of, device) -> dict:
     """paths.PathTable + path_of (S,) -> the device tensors and the mpcg_path_table of
     include/mpcg_path.h (dict coef, knots, n_segments, path_of, path_of_host, native)."""
-    import torch
-
     coef = torch.from_numpy(np.ascontiguousarray(table.coef, np.float64)).to(device)
     knots = torch.from_numpy(np.ascontiguousarray(table.knots, np.float64)).to(device)
     nseg = torch.from_numpy(np.ascontiguousarray(table.n_segments, np.int32)).to(device)
@@ -553,19 +453,16 @@ def path_update_device(pr: MpcgProblem, dtable: dict, state, closest_segment, cl
     path (`dtable`: path_table_device), closest_segment (S,) int32 in / out (-1: not initialised),
     closest_s (S,) float64, the window of n_seg segments into stage_params (S, npar) and reached (S,)
     uint8.  Asynchronous on `stream`; nothing is allocated."""
-    import torch
-
     S = state.shape[0]
-    assert tuple(state.shape) == (S, pr.nx) and tuple(stage_params.shape) == (S, pr.npar)
-    for t_ in (state, closest_s, stage_params):
-        assert t_.dtype == torch.float64 and t_.is_cuda and t_.is_contiguous()
-    assert closest_segment.dtype == torch.int32 and closest_segment.is_contiguous() and closest_segment.numel() == S
-    assert closest_s.numel() == S and dtable["path_of"].numel() == S
-    assert reached.dtype == torch.uint8 and reached.is_contiguous() and reached.numel() == S
-    s = stream if stream is not None else torch.cuda.current_stream(state.device)
+    _dev("state", state, F64, (S, pr.nx))
+    _dev("stage_params", stage_params, F64, (S, pr.npar))
+    _dev("closest_s", closest_s, F64, S)
+    _dev("closest_segment", closest_segment, I32, S)
+    _dev("reached", reached, U8, S)
+    assert dtable["path_of"].numel() == S
     rc = lib.mpcg_path_update(C.byref(pr), S, C.byref(dtable["native"]), dtable["path_of_host"].ctypes.data,
                               _ptr(state), _ptr(closest_segment), _ptr(closest_s), _ptr(stage_params), _ptr(reached),
-                              C.c_void_p(s.cuda_stream))
+                              _stream(stream, state.device))
     _check(rc, "mpcg_path_update")
 
 
@@ -575,29 +472,24 @@ def path_command_device(pr: MpcgProblem, G: int, settings: MpcgPathSettings, bes
     xtraj (S*G, N+1, nx) / utraj (S*G, N, nu) and state (S, nx); with settings.plant, state_next (S, nx)
     from the kinematic stand-in plant, its entry spline_slot set to closest_s (S,).  Asynchronous on
     `stream`; nothing is allocated."""
-    import torch
-
     S, N = state.shape[0], pr.N
-    assert best.dtype == torch.int32 and best.is_contiguous() and best.numel() == S
-    assert tuple(xtraj.shape) == (S * G, N + 1, pr.nx) and tuple(utraj.shape) == (S * G, N, pr.nu)
-    assert tuple(state.shape) == (S, pr.nx) and tuple(cmd.shape) == (S, 2)
-    for t_ in (xtraj, utraj, state, cmd) + tuple(t_ for t_ in (closest_s, state_next) if t_ is not None):
-        assert t_.dtype == torch.float64 and t_.is_cuda and t_.is_contiguous()
+    _dev("best", best, I32, S)
+    _dev("xtraj", xtraj, F64, (S * G, N + 1, pr.nx))
+    _dev("utraj", utraj, F64, (S * G, N, pr.nu))
+    _dev("state", state, F64, (S, pr.nx))
+    _dev("cmd", cmd, F64, (S, 2))
     if state_next is not None:
-        assert tuple(state_next.shape) == (S, pr.nx)
+        _dev("state_next", state_next, F64, (S, pr.nx))
     if closest_s is not None:
-        assert closest_s.numel() == S
-    s = stream if stream is not None else torch.cuda.current_stream(state.device)
+        _dev("closest_s", closest_s, F64, S)
     rc = lib.mpcg_path_command(C.byref(pr), S, G, C.byref(settings), _ptr(best), _ptr(xtraj), _ptr(utraj), _ptr(state),
                                _ptr(closest_s), int(spline_slot), _ptr(cmd), _ptr(state_next),
-                               C.c_void_p(s.cuda_stream))
+                               _stream(stream, state.device))
     _check(rc, "mpcg_path_command")
 
 
 def road_bounds_device(left_coef, right_coef, device) -> dict:
     """The bound tables (P, M, 8) of the bounds mode (roads.stack_bounds) as device tensors."""
-    import torch
-
     t = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float64)).to(device)  # noqa: E731
     return dict(left=t(left_coef), right=t(right_coef))
 
@@ -611,38 +503,34 @@ def road_halfspaces_device(pr: MpcgProblem, G: int, max_obstacles: int, settings
     (S, N+1, 7), or of the braking plan from state (S, nx) when it is None.  `dtable`:
     path_table_device; `bounds`: road_bounds_device, for the bounds mode; halfspaces (S, N, 2, 3),
     optional, receives the rows per scene.  Asynchronous on `stream`; nothing is allocated."""
-    import torch
-
     S, N = dtable["path_of"].numel(), pr.N
-    assert tuple(params.shape) == (S * G, N, pr.npar)
-    for t_ in (params, state, main_warm, halfspaces) + ((bounds["left"], bounds["right"]) if bounds else ()):
-        assert t_ is None or (t_.dtype == torch.float64 and t_.is_cuda and t_.is_contiguous())
-    assert state is None or tuple(state.shape) == (S, pr.nx)
-    assert main_warm is None or tuple(main_warm.shape) == (S, N + 1, pr.nu + pr.nx)
-    assert guided is None or (guided.dtype == torch.uint8 and guided.is_contiguous() and guided.numel() == S * G)
-    assert halfspaces is None or tuple(halfspaces.shape) == (S, N, 2, 3)
+    _dev("params", params, F64, (S * G, N, pr.npar))
+    if state is not None:
+        _dev("state", state, F64, (S, pr.nx))
+    if main_warm is not None:
+        _dev("main_warm", main_warm, F64, (S, N + 1, pr.nu + pr.nx))
+    if guided is not None:
+        _dev("guided", guided, U8, S * G)
+    if halfspaces is not None:
+        _dev("halfspaces", halfspaces, F64, (S, N, 2, 3))
     if bounds:
-        assert tuple(bounds["left"].shape) == tuple(dtable["coef"].shape) == tuple(bounds["right"].shape)
-    io = MpcgRoadIo(None if state is None else state.data_ptr(), None if main_warm is None else main_warm.data_ptr(),
-                    float(deceleration), None if guided is None else guided.data_ptr(),
+        _dev("bounds left", bounds["left"], F64, tuple(dtable["coef"].shape))
+        _dev("bounds right", bounds["right"], F64, tuple(dtable["coef"].shape))
+    io = MpcgRoadIo(_addr(state), _addr(main_warm), float(deceleration), _addr(guided),
                     bounds["left"].data_ptr() if bounds else None, bounds["right"].data_ptr() if bounds else None)
-    s = stream if stream is not None else torch.cuda.current_stream(params.device)
     rc = lib.mpcg_road_halfspaces(C.byref(pr), S, G, int(max_obstacles), C.byref(settings), C.byref(dtable["native"]),
                                   dtable["path_of_host"].ctypes.data, C.byref(io), _ptr(params), _ptr(halfspaces),
-                                  C.c_void_p(s.cuda_stream))
+                                  _stream(stream, params.device))
     _check(rc, "mpcg_road_halfspaces")
 
 
 def _guidance_state(gstate: dict, S: int, G: int, N: int) -> MpcgGuidanceState:
-    import torch
-
     K = 2 * (G - 1)
-    ct, cu, pc, sel, orig = (gstate[k] for k in ("class_traj", "class_used", "planner_class", "selected_topology",
-                                                 "prev_was_original"))
-    for t_, dt_, n in ((ct, torch.float64, S * K * (N + 1) * 2), (cu, torch.uint8, S * K), (pc, torch.int32, S * G),
-                       (sel, torch.int32, S), (orig, torch.uint8, S)):
-        assert t_.dtype == dt_ and t_.is_cuda and t_.is_contiguous() and t_.numel() == n
-    return MpcgGuidanceState(ct.data_ptr(), cu.data_ptr(), pc.data_ptr(), sel.data_ptr(), orig.data_ptr())
+    fields = dict(class_traj=(F64, S * K * (N + 1) * 2), class_used=(U8, S * K), planner_class=(I32, S * G),
+                  selected_topology=(I32, S), prev_was_original=(U8, S))
+    for k, (dtype, n) in fields.items():
+        _dev(k, gstate[k], dtype, n)
+    return MpcgGuidanceState(*(gstate[k].data_ptr() for k in fields))
 
 
 def guidance_update_device(pr: MpcgProblem, S: int, G: int, settings: MpcgGuidanceSettings, state, stage_params, obst,
@@ -656,134 +544,115 @@ def guidance_update_device(pr: MpcgProblem, S: int, G: int, settings: MpcgGuidan
     guidance (S, G, N+1, 4), existing_guidance / previously_selected / consistency_on / enabled (S, G)
     uint8, topology (S, G) int32, n_found (S,) int32, heading (S, 2), sig_mask / sig_side (S, G) int32,
     clearance / cost (S, 8).  Asynchronous on `stream`; nothing is allocated."""
-    import torch
-
     N = pr.N
-    assert tuple(state.shape) == (S, pr.nx) and tuple(stage_params.shape) == (S, pr.npar)
-    assert tuple(obst.shape) == (S, pr.n_ell, N, 5) and tuple(obst_meta.shape) == (S, pr.n_ell, 2)
-    assert tuple(guidance.shape) == (S, G, N + 1, 4) and tuple(heading.shape) == (S, 2)
-    assert tuple(clearance.shape) == (S, GUIDANCE_CANDIDATES) and tuple(cost.shape) == (S, GUIDANCE_CANDIDATES)
-    for t_ in (state, stage_params, obst, obst_meta, guidance, heading, clearance, cost):
-        assert t_.dtype == torch.float64 and t_.is_cuda and t_.is_contiguous()
-    for t_ in (existing_guidance, previously_selected, consistency_on, enabled):
-        assert t_.dtype == torch.uint8 and t_.is_cuda and t_.is_contiguous() and t_.numel() == S * G
-    for t_ in (topology, sig_mask, sig_side):
-        assert t_.dtype == torch.int32 and t_.is_cuda and t_.is_contiguous() and t_.numel() == S * G
-    assert n_found.dtype == torch.int32 and n_found.is_contiguous() and n_found.numel() == S
+    _dev("state", state, F64, (S, pr.nx))
+    _dev("stage_params", stage_params, F64, (S, pr.npar))
+    _dev("obst", obst, F64, (S, pr.n_ell, N, 5))
+    _dev("obst_meta", obst_meta, F64, (S, pr.n_ell, 2))
+    _dev("guidance", guidance, F64, (S, G, N + 1, 4))
+    _dev("heading", heading, F64, (S, 2))
+    _dev("clearance", clearance, F64, (S, GUIDANCE_CANDIDATES))
+    _dev("cost", cost, F64, (S, GUIDANCE_CANDIDATES))
+    for k, t in dict(existing_guidance=existing_guidance, previously_selected=previously_selected,
+                     consistency_on=consistency_on, enabled=enabled).items():
+        _dev(k, t, U8, S * G)
+    for k, t in dict(topology=topology, sig_mask=sig_mask, sig_side=sig_side).items():
+        _dev(k, t, I32, S * G)
+    _dev("n_found", n_found, I32, S)
     st = _guidance_state(gstate, S, G, N)
-    out = MpcgGuidanceOut(*(t_.data_ptr() for t_ in (guidance, existing_guidance, previously_selected, consistency_on,
-                                                     topology, enabled, n_found, heading, sig_mask, sig_side,
-                                                     clearance, cost)))
-    s = stream if stream is not None else torch.cuda.current_stream(state.device)
+    out = MpcgGuidanceOut(*(t.data_ptr() for t in (guidance, existing_guidance, previously_selected, consistency_on,
+                                                   topology, enabled, n_found, heading, sig_mask, sig_side,
+                                                   clearance, cost)))
     rc = lib.mpcg_guidance_update(C.byref(pr), S, G, C.byref(settings), _ptr(state), _ptr(stage_params), _ptr(obst),
-                                  _ptr(obst_meta), C.byref(st), C.byref(out), C.c_void_p(s.cuda_stream))
+                                  _ptr(obst_meta), C.byref(st), C.byref(out), _stream(stream, state.device))
     _check(rc, "mpcg_guidance_update")
 
 
 def guidance_mask_device(S: int, G: int, enabled, exit_code, stream=None):
     """mpcg_guidance_mask: exit_code (S*G,) int32 of the planners with enabled (S, G) 0 becomes
     MPCG_GUIDANCE_EXIT_DISABLED, in place."""
-    import torch
-
-    assert enabled.dtype == torch.uint8 and enabled.is_contiguous() and enabled.numel() == S * G
-    assert exit_code.dtype == torch.int32 and exit_code.is_contiguous() and exit_code.numel() == S * G
-    s = stream if stream is not None else torch.cuda.current_stream(exit_code.device)
-    _check(lib.mpcg_guidance_mask(S, G, _ptr(enabled), _ptr(exit_code), C.c_void_p(s.cuda_stream)),
+    _dev("enabled", enabled, U8, S * G)
+    _dev("exit_code", exit_code, I32, S * G)
+    _check(lib.mpcg_guidance_mask(S, G, _ptr(enabled), _ptr(exit_code), _stream(stream, exit_code.device)),
            "mpcg_guidance_mask")
 
 
 def guidance_select_device(S: int, G: int, best, guided, topology, enabled, gstate: dict, stream=None):
     """mpcg_guidance_select: selected_topology, prev_was_original and planner_class of `gstate` from
     best (S,) int32, guided / enabled (S, G) uint8 and topology (S, G) int32."""
-    import torch
-
-    assert best.dtype == torch.int32 and best.is_contiguous() and best.numel() == S
-    for t_ in (guided, enabled):
-        assert t_.dtype == torch.uint8 and t_.is_contiguous() and t_.numel() == S * G
-    assert topology.dtype == torch.int32 and topology.is_contiguous() and topology.numel() == S * G
+    _dev("best", best, I32, S)
+    _dev("guided", guided, U8, S * G)
+    _dev("enabled", enabled, U8, S * G)
+    _dev("topology", topology, I32, S * G)
     N = gstate["class_traj"].shape[2] - 1
     st = _guidance_state(gstate, S, G, N)
-    s = stream if stream is not None else torch.cuda.current_stream(best.device)
     _check(lib.mpcg_guidance_select(S, G, _ptr(best), _ptr(guided), _ptr(topology), _ptr(enabled), C.byref(st),
-                                    C.c_void_p(s.cuda_stream)), "mpcg_guidance_select")
+                                    _stream(stream, best.device)), "mpcg_guidance_select")
 
 
 def active_plan_device(enabled, slot_of=None, solve_of=None, n_active=None, stream=None):
     """mpcg_active_plan (include/mpcg_active.h): the stable compaction of enabled (B,) uint8 (any shape
     of B elements).  Returns slot_of (B,), solve_of (B,) and n_active (1,), int32 device tensors
     (allocated unless given); asynchronous on `stream`."""
-    import torch
-
-    assert enabled.dtype == torch.uint8 and enabled.is_cuda and enabled.is_contiguous()
+    _dev("enabled", enabled, U8)
     B, dev = enabled.numel(), enabled.device
-    slot_of = torch.empty((B,), dtype=torch.int32, device=dev) if slot_of is None else slot_of
-    solve_of = torch.empty((B,), dtype=torch.int32, device=dev) if solve_of is None else solve_of
-    n_active = torch.empty((1,), dtype=torch.int32, device=dev) if n_active is None else n_active
-    for t_, n in ((slot_of, B), (solve_of, B), (n_active, 1)):
-        assert t_.dtype == torch.int32 and t_.is_cuda and t_.is_contiguous() and t_.numel() == n
-    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    slot_of = torch.empty((B,), dtype=I32, device=dev) if slot_of is None else slot_of
+    solve_of = torch.empty((B,), dtype=I32, device=dev) if solve_of is None else solve_of
+    n_active = torch.empty((1,), dtype=I32, device=dev) if n_active is None else n_active
+    _dev("slot_of", slot_of, I32, B)
+    _dev("solve_of", solve_of, I32, B)
+    _dev("n_active", n_active, I32, 1)
     # (an empty tensor's data_ptr is 0: the plan of an empty batch still needs non-null pointers)
-    p = lambda t_: C.c_void_p(t_.data_ptr() or n_active.data_ptr())  # noqa: E731
-    _check(lib.mpcg_active_plan(B, p(enabled), p(slot_of), p(solve_of), _ptr(n_active), C.c_void_p(s.cuda_stream)),
+    p = lambda t: C.c_void_p(t.data_ptr() or n_active.data_ptr())  # noqa: E731
+    _check(lib.mpcg_active_plan(B, p(enabled), p(slot_of), p(solve_of), _ptr(n_active), _stream(stream, dev)),
            "mpcg_active_plan")
     return slot_of, solve_of, n_active
 
 
-_IO_KEYS = (("params", "params"), ("warm", "warm"), ("xinit", "xinit"), ("lam_in", "lam_in"), ("xtraj", "xtraj"),
-            ("utraj", "utraj"), ("pobj", "pobj"), ("exit_code", "exit"), ("info", "info"), ("lam_out", "lam"),
-            ("qp_in", "qp_in"), ("qp_out", "qp"), ("stats", "stats"))
+# mpcg_io's fields in order, as the keys of solve_batch_device's arguments and result
+_IO_KEYS = ("params", "warm", "xinit", "lam_in", "xtraj", "utraj", "pobj", "exit", "info", "lam", "qp_in", "qp",
+            "stats")
 
 
 def _active_io(pr: MpcgProblem, d: dict, rows: int) -> MpcgIo:
     """An mpcg_io over the tensors of `d` (keys of solve_batch_device's arguments and result: params, warm,
     xinit, lam_in, qp_in, xtraj, utraj, pobj, exit, info, lam, qp, stats; missing or None: NULL), each
     checked to hold at least `rows` blocks of the size include/mpcg.h documents."""
-    import torch
-
     N, nx, nu = pr.N, pr.nx, pr.nu
     LS = lam_stride(pr)
     Q = qp_mem_size(pr) if (d.get("qp_in") is not None or d.get("qp") is not None) else 0
     block = dict(params=N * pr.npar, warm=(N + 1) * (nu + nx), xinit=nx, lam_in=N * LS, xtraj=(N + 1) * nx,
                  utraj=N * nu, pobj=1, exit=1, info=INFO_STRIDE, lam=N * LS, qp_in=Q, qp=Q, stats=STATS_STRIDE)
-    ptrs = []
-    for _, k in _IO_KEYS:
-        t_ = d.get(k)
-        if t_ is not None:
-            want = torch.int32 if k in ("exit", "info") else torch.float64
-            assert t_.dtype == want and t_.is_cuda and t_.is_contiguous(), k
-            assert t_.numel() >= rows * block[k] and (t_.shape[0] == 0 or t_.numel() == t_.shape[0] * block[k]), \
-                (k, tuple(t_.shape), rows, block[k])
-        ptrs.append(None if t_ is None else t_.data_ptr())
-    return MpcgIo(*ptrs)
+    for k in _IO_KEYS:
+        t = d.get(k)
+        if t is not None:
+            _dev(k, t, I32 if k in ("exit", "info") else F64)
+            assert t.numel() >= rows * block[k] and (t.shape[0] == 0 or t.numel() == t.shape[0] * block[k]), \
+                (k, tuple(t.shape), rows, block[k])
+    return MpcgIo(*(_addr(d.get(k)) for k in _IO_KEYS))
 
 
 def active_gather_device(pr: MpcgProblem, slot_of, full: dict, dense: dict, stream=None):
     """mpcg_active_gather: params, warm, xinit (and lam_in / qp_in where present in both) of every enabled
     solve b of `full` (B rows) into row slot_of[b] of `dense` (at least as many rows as are enabled; the
     caller's responsibility, B rows always suffice).  Dicts of device tensors, keys as in _active_io."""
-    import torch
-
     B = slot_of.numel()
-    assert slot_of.dtype == torch.int32 and slot_of.is_cuda and slot_of.is_contiguous()
+    _dev("slot_of", slot_of, I32)
     assert full["params"].shape[0] == B
     fio, dio = _active_io(pr, full, B), _active_io(pr, dense, 0)
-    s = stream if stream is not None else torch.cuda.current_stream(slot_of.device)
     _check(lib.mpcg_active_gather(C.byref(pr), B, _ptr(slot_of), C.byref(fio), C.byref(dio),
-                                  C.c_void_p(s.cuda_stream)), "mpcg_active_gather")
+                                  _stream(stream, slot_of.device)), "mpcg_active_gather")
 
 
 def active_scatter_device(pr: MpcgProblem, slot_of, dense: dict, full: dict, stream=None):
     """mpcg_active_scatter: every output present in `full` (xtraj, utraj, pobj, exit, info, lam, qp, stats; B
     rows) from row slot_of[b] of `dense`; a disabled solve gets the fill of include/mpcg_active.h, which
     reads full["warm"]."""
-    import torch
-
     B = slot_of.numel()
-    assert slot_of.dtype == torch.int32 and slot_of.is_cuda and slot_of.is_contiguous()
+    _dev("slot_of", slot_of, I32)
     fio, dio = _active_io(pr, full, B), _active_io(pr, dense, 0)
-    s = stream if stream is not None else torch.cuda.current_stream(slot_of.device)
     _check(lib.mpcg_active_scatter(C.byref(pr), B, _ptr(slot_of), C.byref(dio), C.byref(fio),
-                                   C.c_void_p(s.cuda_stream)), "mpcg_active_scatter")
+                                   _stream(stream, slot_of.device)), "mpcg_active_scatter")
 
 
 class ActiveWorkspace:
@@ -819,53 +688,22 @@ def solve_active_device(pr: MpcgProblem, params, warm, xinit, enabled, ws=None, 
     Returns solve_batch_device's dict plus n_active (int) and slot_of (B,) int32.  Synchronises `stream`
     once (the count is read on the host; not capturable into a graph) and returns with the solve and the
     scatter in flight on it."""
-    import torch
-
-    B = params.shape[0]
-    N, nx, NU = pr.N, pr.nx, pr.nu
-    LS = lam_stride(pr)
-    dev = params.device
-    for t_, shape in ((params, (B, N, pr.npar)), (warm, (B, N + 1, NU + nx)), (xinit, (B, nx))):
-        assert t_.dtype == torch.float64 and t_.is_cuda and t_.is_contiguous() and tuple(t_.shape) == shape, \
-            (tuple(t_.shape), shape)
-    assert enabled.dtype == torch.uint8 and enabled.is_cuda and enabled.is_contiguous() and enabled.numel() == B
-    if lam_in is not None:
-        assert tuple(lam_in.shape) == (B, N, LS) and lam_in.is_contiguous() and lam_in.dtype == torch.float64
+    B, dev = params.shape[0], params.device
+    out = _solve_outputs(pr, B, dev, out, lam_out, qp_out, stats)
+    if "slot_of" not in out:
+        out["slot_of"] = torch.empty((B,), dtype=I32, device=dev)
+    io = _solve_io(pr, params, warm, xinit, lam_in, qp_in, out, lam_out, qp_out, stats)
+    _dev("enabled", enabled, U8, B)
     own = ws is None
     if own:
         ws = ActiveWorkspace(pr, max(B, 1), with_lam=lam_in is not None or lam_out,
                              with_qp=qp_in is not None or qp_out, with_stats=stats)
-    if out is None:
-        out = dict(xtraj=torch.empty((B, N + 1, nx), dtype=torch.float64, device=dev),
-                   utraj=torch.empty((B, N, NU), dtype=torch.float64, device=dev),
-                   pobj=torch.empty((B,), dtype=torch.float64, device=dev),
-                   exit=torch.empty((B,), dtype=torch.int32, device=dev),
-                   info=torch.empty((B, INFO_STRIDE), dtype=torch.int32, device=dev))
-    if lam_out and "lam" not in out:
-        out["lam"] = torch.empty((B, N, LS), dtype=torch.float64, device=dev)
-    Q = qp_mem_size(pr) if (qp_in is not None or qp_out) else 0
-    if qp_in is not None:
-        assert tuple(qp_in.shape) == (B, Q) and qp_in.is_contiguous() and qp_in.dtype == torch.float64
-    if qp_out and "qp" not in out:
-        out["qp"] = torch.empty((B, Q), dtype=torch.float64, device=dev)
-    if stats and "stats" not in out:
-        out["stats"] = torch.empty((B, STATS_STRIDE), dtype=torch.float64, device=dev)
-    if "slot_of" not in out:
-        out["slot_of"] = torch.empty((B,), dtype=torch.int32, device=dev)
     s = stream if stream is not None else torch.cuda.current_stream(dev)
-    io = MpcgIo(params.data_ptr(), warm.data_ptr(), xinit.data_ptr(),
-                None if lam_in is None else lam_in.data_ptr(),
-                out["xtraj"].data_ptr(), out["utraj"].data_ptr(), out["pobj"].data_ptr(), out["exit"].data_ptr(),
-                out["info"].data_ptr() if out.get("info") is not None else None,
-                out["lam"].data_ptr() if lam_out else None,
-                None if qp_in is None else qp_in.data_ptr(),
-                out["qp"].data_ptr() if qp_out else None,
-                out["stats"].data_ptr() if stats else None)
     n = C.c_int(-1)
     try:
         _check(lib.mpcg_solve_active(C.byref(pr), B, C.byref(io), _ptr(enabled), ws._c, C.byref(n),
-                                     C.c_void_p(s.cuda_stream)), "mpcg_solve_active")
-        _check(lib.mpcg_active_ws_read_plan(ws._c, B, _ptr(out["slot_of"]), None, C.c_void_p(s.cuda_stream)),
+                                     _stream(s, dev)), "mpcg_solve_active")
+        _check(lib.mpcg_active_ws_read_plan(ws._c, B, _ptr(out["slot_of"]), None, _stream(s, dev)),
                "mpcg_active_ws_read_plan")
     finally:
         if own:

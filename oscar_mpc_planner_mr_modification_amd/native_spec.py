@@ -155,12 +155,6 @@ class MpcgScenarioIo(C.Structure):
 
 
 ABI_VERSION = 9
-EXPORTS = ("mpcg_abi_version", "mpcg_last_error", "mpcg_supported", "mpcg_num_h", "mpcg_lam_size", "mpcg_qp_mem_size",
-           "mpcg_problem_from_map", "mpcg_problem_from_map_model", "mpcg_solve", "mpcg_context_create", "mpcg_context_destroy",
-           "mpcg_context_solve", "mpcg_context_set_iterations", "mpcg_solve_batch_device", "mpcg_solve_batch_host", "mpcg_select_best_device", "mpcg_prepare", "mpcg_advance",
-           "mpcg_prepare_scenario", "mpcg_select_lowest_cost_device", "mpcg_winner_records_device",
-           "mpcg_release_stream_workspace",
-           "mpcg_instance_traits", "mpcg_problem_set_qp_profile")
 
 
 class MpcgFleetSettings(C.Structure):
@@ -178,9 +172,6 @@ class MpcgFleetState(C.Structure):
                 ("prev_topology", C.c_void_p)]
 
 
-# the multi-robot layer (include/mpcg_fleet.h), exported from the same library; listed apart from
-# EXPORTS, which mirrors include/mpcg.h
-FLEET_EXPORTS = ("mpcg_fleet_obstacles", "mpcg_fleet_publish")
 # mpcg_fleet_publish's reason (CommunicationTriggerReason)
 FLEET_REASONS = {0: "NO_COMMUNICATION", 1: "INFEASIBLE", 3: "TOPOLOGY_CHANGE", 4: "GEOMETRIC", 5: "TIME",
                  6: "NON_GUIDED_HOMOLOGY_FAIL"}
@@ -197,10 +188,8 @@ class MpcgPathSettings(C.Structure):
     _fields_ = [("control_frequency", C.c_double), ("deceleration", C.c_double), ("plant", C.c_int)]
 
 
-# the reference-path tracking (include/mpcg_path.h), exported from the same library
-PATH_EXPORTS = ("mpcg_path_update", "mpcg_path_command")
+# the reference-path tracking (include/mpcg_path.h)
 PATH_MAX_SEGMENTS, PATH_SAMPLES, PATH_ROUNDS, PATH_REACHED_RADIUS = 64, 64, 5, 1.5
-
 
 
 class MpcgRoadSettings(C.Structure):
@@ -214,8 +203,7 @@ class MpcgRoadIo(C.Structure):
                 ("guided", C.c_void_p), ("left_coef", C.c_void_p), ("right_coef", C.c_void_p)]
 
 
-# the road-boundary halfspaces (include/mpcg_road.h), exported from the same library
-ROAD_EXPORTS = ("mpcg_road_halfspaces",)
+# the road-boundary halfspaces (include/mpcg_road.h)
 ROAD_CENTERLINE, ROAD_BOUNDS, ROAD_MAX_N = 0, 1, 32
 
 
@@ -238,15 +226,93 @@ class MpcgGuidanceOut(C.Structure):
                 ("clearance", C.c_void_p), ("cost", C.c_void_p)]
 
 
-# the guidance layer (include/mpcg_guidance.h), exported from the same library
-GUIDANCE_EXPORTS = ("mpcg_guidance_update", "mpcg_guidance_mask", "mpcg_guidance_select")
+# the guidance layer (include/mpcg_guidance.h)
 GUIDANCE_CANDIDATES, GUIDANCE_BITS, GUIDANCE_FINE, GUIDANCE_SWEEPS = 8, 3, 4, 4
 GUIDANCE_MAX_N, GUIDANCE_MAX_ELL, GUIDANCE_MAX_SEG = 32, 32, 8
 GUIDANCE_ACCEL, GUIDANCE_RELEVANT, GUIDANCE_OFFSET, GUIDANCE_WIDTH, GUIDANCE_ONSET = 1.0, 2.5, 1.2, 2.0, 0.8
 GUIDANCE_PUSH_MARGIN, GUIDANCE_CLEARANCE, GUIDANCE_V_FLOOR = 0.75, 0.25, 1e-3
 GUIDANCE_EXIT_DISABLED = -100
 
-# the active-solve compaction (include/mpcg_active.h), exported from the same library
-ACTIVE_EXPORTS = ("mpcg_active_plan", "mpcg_active_gather", "mpcg_active_scatter", "mpcg_active_ws_create",
-                  "mpcg_active_ws_destroy", "mpcg_active_ws_read_plan", "mpcg_solve_active")
+# the active-solve compaction (include/mpcg_active.h)
 ACTIVE_EXIT_SKIPPED = -100
+
+
+def _signatures() -> dict:
+    i, d, vp, ptr = C.c_int, C.c_double, C.c_void_p, C.POINTER
+    P, IO = ptr(MpcgProblem), ptr(MpcgIo)
+    FS, FT, GT = ptr(MpcgFleetSettings), ptr(MpcgFleetState), ptr(MpcgGuidanceState)
+    strs, ints, dbls = ptr(C.c_char_p), ptr(i), ptr(d)
+    return {
+        "mpcg.h": {
+            "mpcg_abi_version": (i, []),
+            "mpcg_last_error": (C.c_char_p, []),
+            "mpcg_supported": (i, [P]),
+            "mpcg_num_h": (i, [P]),
+            "mpcg_lam_size": (i, [P]),
+            "mpcg_qp_mem_size": (i, [P]),
+            "mpcg_problem_from_map": (i, [P, i, i, i, i, strs, ints, dbls, dbls, d, i]),
+            "mpcg_problem_from_map_model": (i, [P, i, i, i, i, i, strs, ints, dbls, dbls, d, i]),
+            "mpcg_solve": (i, [P, i, IO, vp]),
+            "mpcg_context_create": (vp, [P, i]),
+            "mpcg_context_destroy": (None, [vp]),
+            "mpcg_context_solve": (i, [vp, i, IO]),
+            "mpcg_context_set_iterations": (i, [vp, i]),
+            "mpcg_solve_batch_device": (i, [P, i] + [vp] * 9),
+            "mpcg_solve_batch_host": (i, [P, i] + [vp] * 8),
+            "mpcg_select_best_device": (i, [i, i, i, vp, vp, vp, vp, d, vp, vp, d, vp, vp, vp, vp]),
+            "mpcg_prepare": (i, [P, i, i, ptr(MpcgSceneIo)] + [vp] * 6),
+            "mpcg_advance": (i, [P, i, i, ptr(MpcgStepIo)] + [vp] * 7),
+            "mpcg_prepare_scenario": (i, [P, i, i, ptr(MpcgScenarioIo)] + [vp] * 4),
+            "mpcg_select_lowest_cost_device": (i, [i, i, vp, vp, vp, vp]),
+            "mpcg_winner_records_device": (i, [i, i, i, i, i] + [vp] * 6),
+            "mpcg_release_stream_workspace": (i, [vp]),
+            "mpcg_instance_traits": (i, [P, C.c_char_p, i]),
+            "mpcg_problem_set_qp_profile": (i, [P, i]),
+        },
+        "mpcg_fleet.h": {
+            "mpcg_fleet_obstacles": (i, [P, i, i, i, FS, FT, vp, vp, vp, vp, d, vp, vp, vp]),
+            "mpcg_fleet_publish": (i, [P, i, i, i, FS, FT, vp, vp, vp, vp, vp, d, vp, vp, vp]),
+        },
+        "mpcg_path.h": {
+            "mpcg_path_update": (i, [P, i, ptr(MpcgPathTable)] + [vp] * 7),
+            "mpcg_path_command": (i, [P, i, i, ptr(MpcgPathSettings), vp, vp, vp, vp, vp, i, vp, vp, vp]),
+        },
+        "mpcg_road.h": {
+            "mpcg_road_halfspaces": (i, [P, i, i, i, ptr(MpcgRoadSettings), ptr(MpcgPathTable), vp, ptr(MpcgRoadIo),
+                                         vp, vp, vp]),
+        },
+        "mpcg_guidance.h": {
+            "mpcg_guidance_update": (i, [P, i, i, ptr(MpcgGuidanceSettings), vp, vp, vp, vp, GT, ptr(MpcgGuidanceOut),
+                                         vp]),
+            "mpcg_guidance_mask": (i, [i, i, vp, vp, vp]),
+            "mpcg_guidance_select": (i, [i, i, vp, vp, vp, vp, GT, vp]),
+        },
+        "mpcg_active.h": {
+            "mpcg_active_plan": (i, [i, vp, vp, vp, vp, vp]),
+            "mpcg_active_gather": (i, [P, i, vp, IO, IO, vp]),
+            "mpcg_active_scatter": (i, [P, i, vp, IO, IO, vp]),
+            "mpcg_active_ws_create": (vp, [P, i, i, i, i]),
+            "mpcg_active_ws_destroy": (None, [vp]),
+            "mpcg_active_ws_read_plan": (i, [vp, i, vp, vp, vp]),
+            "mpcg_solve_active": (i, [P, i, IO, vp, vp, ints, vp]),
+        },
+        # exported without a public header: instance registration (csrc/mpcg_instance.h), test and
+        # diagnostic hooks (mpcg_kernels.hip)
+        None: {
+            "mpcg_rejected_instances": (i, []),
+            "mpcg_debug_set_queue": (i, [vp, C.c_uint]),
+            "mpcg_debug_set_stamp_buffer": (None, [vp]),
+        },
+    }
+
+
+# Every function of libmpcg.so that Python calls, by the public header under include/ that declares it:
+# name -> (restype, argtypes).  native._load() applies it; a new layer adds its group here
+# (DESIGN.md "The host-side seam").  The *_EXPORTS tuples are the groups' names.
+SIGNATURES = _signatures()
+EXPORTS = tuple(SIGNATURES["mpcg.h"])
+FLEET_EXPORTS = tuple(SIGNATURES["mpcg_fleet.h"])
+PATH_EXPORTS = tuple(SIGNATURES["mpcg_path.h"])
+ROAD_EXPORTS = tuple(SIGNATURES["mpcg_road.h"])
+GUIDANCE_EXPORTS = tuple(SIGNATURES["mpcg_guidance.h"])
+ACTIVE_EXPORTS = tuple(SIGNATURES["mpcg_active.h"])

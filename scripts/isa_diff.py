@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """Kernel-by-kernel comparison of the gfx950 assembly of two source trees (CPU only).
 
-    python scripts/isa_diff.py OLD_ROOT NEW_ROOT [--expect identical|abi] [--out FILE] [-D...]
+    python scripts/isa_diff.py OLD_ROOT NEW_ROOT [--expect identical|abi] [--units families|library|all]
+                               [--out FILE] [-D...]
 
-Compiles the four built-in instance families of both trees with the library's flags plus
+Compiles the built-in instance families of both trees with the library's flags plus
 `--cuda-device-only -S` (or reuses `<family>.s` files: --old-asm / --new-asm DIR), replaces every
 sqp_kernel symbol by `sqp_kernel<Cfg<...>,FULL,PROF>` -- so a template parameter or kernel argument
 added or removed after those three does not show as a renamed symbol -- and compares, per kernel,
@@ -25,10 +26,16 @@ Differences are sorted into classes:
 --expect identical: only `cuid` may differ.  --expect abi: the five classes above `other` may.
 Instruction count, VGPR, AGPR, scratch and LDS of every kernel must be equal in both modes.
 Exit status 0 when the expectation holds, 1 otherwise.
+
+--units library compares the other translation units of libmpcg.so instead (mpcg_kernels.hip,
+mpcg_prepare.hip and the layers; --units all: both), each with its own flags, the list and the flags
+taken from `_build.lib_sources()` of NEW_ROOT.  Their kernels are no sqp_kernel instances, so a unit
+is compared as a whole, as the remainder of a family's unit is: any line that differs is `other`.
 """
 from __future__ import annotations
 
 import argparse
+import importlib.util
 import os
 import re
 import subprocess
@@ -36,28 +43,37 @@ import sys
 import tempfile
 from concurrent.futures import ThreadPoolExecutor
 
-FAMILIES = ["mpcg_inst_tmpc20", "mpcg_inst_tmpc30", "mpcg_inst_shmpc", "mpcg_inst_bicycle"]
+FAMILIES = ["mpcg_inst_tmpc20", "mpcg_inst_tmpc30", "mpcg_inst_shmpc", "mpcg_inst_bicycle", "mpcg_inst_road"]
 PKG = "oscar_mpc_planner_mr_modification_amd"
 KSYM = re.compile(r"_ZN4mpcg10sqp_kernelINS_3CfgI((?:Li\d+E)+)EELb([01])ELi(\d+)E(?:Li\d+E)*EEv12mpcg_problemi7mpcg_ioPyPdPji?")
 REST = "(rest of the translation unit)"
 ABI_CLASSES = {"cuid", "arg-metadata", "kernarg-size", "hidden-arg-load", "s_add-imm"}
 
 
-def compile_tree(root: str, out_dir: str, defines) -> None:
+def library_units(root: str) -> dict:
+    """unit -> flags of the translation units of `root`'s libmpcg.so that are no instance family"""
+    spec = importlib.util.spec_from_file_location("_isa_diff_build", os.path.join(root, PKG, "_build.py"))
+    build = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(build)
+    return {src[:-len(".hip")]: flags for src, flags in build.lib_sources().items() if src[:-len(".hip")] not in FAMILIES}
+
+
+def compile_tree(root: str, out_dir: str, defines, units: dict) -> None:
+    """`units`: unit -> its extra flags"""
     csrc = os.path.join(root, PKG, "csrc")
     arch = os.environ.get("MPCG_OFFLOAD_ARCH", "gfx950")
 
     def one(fam):
         cmd = ["hipcc", f"--offload-arch={arch}", "-O3", "-std=c++17", "-fPIC", f"-I{os.path.join(root, 'include')}",
-               f"-I{csrc}", *defines, "--cuda-device-only", "-S", os.path.join(csrc, fam + ".hip"), "-o",
+               f"-I{csrc}", *units[fam], *defines, "--cuda-device-only", "-S", os.path.join(csrc, fam + ".hip"), "-o",
                os.path.join(out_dir, fam + ".s")]
         r = subprocess.run(cmd, stderr=subprocess.PIPE, text=True)
         if r.returncode != 0:
             sys.stderr.write(r.stderr)
             raise subprocess.CalledProcessError(r.returncode, cmd)
 
-    with ThreadPoolExecutor(len(FAMILIES)) as ex:
-        list(ex.map(one, FAMILIES))
+    with ThreadPoolExecutor(min(len(units), os.cpu_count() or 4)) as ex:
+        list(ex.map(one, units))
 
 
 def norm_sym(text: str) -> str:
@@ -189,17 +205,22 @@ def main() -> int:
     ap.add_argument("--old-asm", help="directory of <family>.s already compiled from old_root")
     ap.add_argument("--new-asm", help="directory of <family>.s already compiled from new_root")
     ap.add_argument("--expect", choices=["identical", "abi"], default="identical")
+    ap.add_argument("--units", choices=["families", "library", "all"], default="families",
+                    help="the instance families, the other translation units of libmpcg.so, or both")
     ap.add_argument("--out", help="write the report here as well")
     ap.add_argument("-D", dest="defines", action="append", default=[], help="extra define for both trees")
     a = ap.parse_args()
     defines = ["-D" + d for d in a.defines]
+    units = {} if a.units == "library" else {fam: [] for fam in FAMILIES}
+    if a.units != "families":
+        units.update(library_units(a.new_root))
     tmp = tempfile.mkdtemp(prefix="isa_diff_")
     dirs = []
     for root, asm, tag in ((a.old_root, a.old_asm, "old"), (a.new_root, a.new_asm, "new")):
         if not asm:
             asm = os.path.join(tmp, tag)
             os.makedirs(asm)
-            compile_tree(root, asm, defines)
+            compile_tree(root, asm, defines, units)
         dirs.append(asm)
 
     out = []
@@ -210,7 +231,7 @@ def main() -> int:
     def note(cls, n=1):
         classes[cls] = classes.get(cls, 0) + n
 
-    for fam in FAMILIES:
+    for fam in units:
         ko, kn = (parse(os.path.join(d, fam + ".s")) for d in dirs)
         if sorted(ko) != sorted(kn):
             out.append(f"{fam}: kernel sets differ: only old {sorted(set(ko) - set(kn))}, only new {sorted(set(kn) - set(ko))}")
@@ -222,6 +243,11 @@ def main() -> int:
             note("other", nd)
             n_lines += nd
             out.append(f"{fam}: {nd} lines outside the kernels differ")
+        if fam not in FAMILIES:
+            nk = sum(1 for x in rn_ if x.startswith(".amdhsa_kernel "))
+            n_kernels += nk
+            out.append(f"{fam:44s} {nk} kernels, {len(rn_)} lines, flags {' '.join(units[fam]) or '-'} | "
+                       f"{'identical' if ro_ == rn_ else 'DIFFERS'}")
         for name in sorted(set(ko) & set(kn)):
             n_kernels += 1
             o, w = ko[name], kn[name]

@@ -4,7 +4,6 @@ the others, the composite around a solve function, the library's exports and err
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -162,24 +161,6 @@ def test_solve_active_host_solves_the_enabled_solves_only():
 # ------------------------------------------------------------------ the C ABI
 
 
-def declared_functions():
-    txt = re.sub(r"/\*.*?\*/", "", open(HDR).read(), flags=re.S)
-    return sorted(set(re.findall(r"^\s*(?:int|void|mpcg_active_ws)\s*\**\s*(mpcg_\w+)\s*\(", txt, re.M)))
-
-
-def test_library_exports_every_function_of_the_active_header():
-    names = declared_functions()
-    assert names == ["mpcg_active_gather", "mpcg_active_plan", "mpcg_active_scatter", "mpcg_active_ws_create",
-                     "mpcg_active_ws_destroy", "mpcg_active_ws_read_plan", "mpcg_solve_active"]
-    assert set(ns.ACTIVE_EXPORTS) == set(names)
-    out = subprocess.run(["nm", "-D", "--defined-only", LIB], capture_output=True, text=True, check=True).stdout
-    exported = set(l.split()[-1] for l in out.splitlines() if l.strip())
-    lib = C.CDLL(LIB)
-    for n in names:
-        assert n in exported, n
-        assert getattr(lib, n) is not None
-
-
 def test_skipped_exit_code_is_the_guidance_layers_disabled_code():
     assert ns.ACTIVE_EXIT_SKIPPED == ns.GUIDANCE_EXIT_DISABLED == -100
     macro = lambda path, name: int(re.search(rf"#define {name} \((-?\d+)\)", open(path).read()).group(1))  # noqa: E731
@@ -190,8 +171,8 @@ def test_skipped_exit_code_is_the_guidance_layers_disabled_code():
 
 def test_active_sources_are_linked_outside_the_source_hash():
     from oscar_mpc_planner_mr_modification_amd import _build
-    assert _build.ACTIVE_SOURCES == {"mpcg_active.hip": ["-ffp-contract=off"]}
-    assert _build.ACTIVE_HEADERS == ["mpcg_active.h"]
+    assert _build.LAYERS["mpcg_active.h"] == {"sources": {"mpcg_active.hip": ["-ffp-contract=off"]},
+                                              "headers": ["mpcg_active.h"]}
     assert "mpcg_active.hip" not in _build.SOURCES and "mpcg_active.h" not in _build.HEADERS
 
 

@@ -228,8 +228,10 @@ def test_road_entry_point_is_exported_and_checks_its_arguments():
     lib = C.CDLL(os.path.join(PKG, "libmpcg.so"))
     for name in ROAD_EXPORTS:
         assert hasattr(lib, name), name
-    assert _build.ROAD_SOURCES == {"mpcg_road.hip": ["-ffp-contract=off"]}
-    assert "mpcg_road.hip" not in _build.SOURCES and "mpcg_road.h" not in _build.HEADERS
+    assert _build.LAYERS["mpcg_road.h"] == {"sources": {"mpcg_road.hip": ["-ffp-contract=off"]},
+                                            "headers": ["mpcg_road.h"]}
+    assert "mpcg_spline.h" in _build.LAYER_SHARED_HEADERS and "mpcg_host.h" in _build.LAYER_SHARED_HEADERS
+    assert "mpcg_road.hip" not in _build.SOURCES and not {"mpcg_road.h", "mpcg_spline.h"} & set(_build.HEADERS)
     assert "mpcg_inst_road.hip" in _build.SOURCES
     lib.mpcg_last_error.restype = C.c_char_p
     fn = lib.mpcg_road_halfspaces
@@ -256,9 +258,24 @@ def test_road_entry_point_is_exported_and_checks_its_arguments():
     assert call(c2r, mo=9) == -1 and call(c2r, mo=-1) == -1
     big = problem_from_layout(tmpc_layout(N=33, max_obstacles=4, add_halfspaces=2))
     assert call(big, mo=4) == -1 and b"N <= 32" in lib.mpcg_last_error()
-    assert call(c2r, table=MpcgPathTable(d, d, d, d, 1, 65)) == -1 and b"M <= 64" in lib.mpcg_last_error()
-    assert call(c2r, table=MpcgPathTable(d, d, d, d, 0, 4)) == -1
-    assert call(c2r, table=MpcgPathTable(None, d, d, d, 1, 4)) == -1
+    # the path-table and path_of checks it shares with mpcg_path_update (tests/test_paths.py), text for text
+    def bad(rc, text):
+        assert rc == -1 and lib.mpcg_last_error().decode() == "mpcg_road_halfspaces: " + text, lib.mpcg_last_error()
+
+    for field in ("coef", "knots", "n_segments", "path_of"):
+        nulled = MpcgPathTable(d, d, d, d, 1, 4)
+        setattr(nulled, field, None)
+        bad(call(c2r, table=nulled), "null path table")
+    bad(fn(C.byref(c2r), 1, 2, 8, C.byref(st), None, po.ctypes.data, C.byref(io), d, None, None), "null path table")
+    bad(call(c2r, table=MpcgPathTable(d, d, d, d, 1, 65)), "needs 1 <= M <= 64 segments per path")
+    bad(call(c2r, table=MpcgPathTable(d, d, d, d, 1, 0)), "needs 1 <= M <= 64 segments per path")
+    bad(call(c2r, table=MpcgPathTable(d, d, d, d, 0, 4)), "needs at least one path")
+    bad(call(c2r, path_of=np.array([1], np.int32)), "path_of[0] = 1 outside the table")
+    bad(call(c2r, path_of=np.array([-1], np.int32)), "path_of[0] = -1 outside the table")
+    # the table is checked before the mode, the mode before path_of
+    bad(call(c2r, table=MpcgPathTable(d, d, d, d, 1, 65), sett=MpcgRoadSettings(6.0, 0.325, 0, 2)),
+        "needs 1 <= M <= 64 segments per path")
+    bad(call(c2r, sett=MpcgRoadSettings(6.0, 0.325, 0, 2), path_of=np.array([1], np.int32)), "unknown mode")
     assert call(c2r, sett=MpcgRoadSettings(6.0, 0.325, 0, 2)) == -1
     assert call(c2r, sett=MpcgRoadSettings(6.0, 0.325, 0, 1)) == -1 and b"bound tables" in lib.mpcg_last_error()
     assert call(c2r, path_of=np.array([1], np.int32)) == -1 and b"outside the table" in lib.mpcg_last_error()
