@@ -218,6 +218,12 @@ int mpcg_solve(const mpcg_problem *pr, int batch, const mpcg_io *io, void *strea
 /* Frees the workspace mpcg_solve keeps for `stream` (after the stream's work).  Returns 0. */
 int mpcg_release_stream_workspace(void *stream);
 
+/* Tests only.  The work-queue launches of the N <= 20 unicycle instances without the slack state take the
+ * last K solves of a batch one SQP-RTI iteration per queue ticket (K a fixed multiple of the resident
+ * workgroups; results do not depend on K).  This forces K = k for the next lean launches on `stream`
+ * (clamped to the batch; 0: every solve whole); k < 0 restores the default.  Returns 0. */
+int mpcg_debug_set_tail_levels(void *stream, int k);
+
 /* A persistent solve context: device buffers and pinned staging for up to
  * `max_batch` solves plus a private stream, so that one Solver::solve()
  * (batch 1) or one GuidanceConstraints::optimize fan-out (batch = guesses)

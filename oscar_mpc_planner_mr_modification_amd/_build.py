@@ -20,7 +20,7 @@ SOURCES = {"mpcg_kernels.hip": [], "mpcg_prepare.hip": ["-ffp-contract=off"],
            "mpcg_inst_tmpc20.hip": [], "mpcg_inst_tmpc30.hip": [], "mpcg_inst_shmpc.hip": [],
            "mpcg_inst_bicycle.hip": [], "mpcg_inst_road.hip": []}
 HEADERS = ["mpcg_device.h", "mpcg_sqp.h", "mpcg_sqp_body.inc", "mpcg_prepare.h", "mpcg_braking.h", "mpcg_bicycle.h",
-           "mpcg_instance.h"]
+           "mpcg_instance.h", "mpcg_tail.h"]
 # the layers around the SQP kernel, by public header under include/ (multi-robot fleet, reference-path
 # tracking, guidance, active-solve compaction, road-boundary halfspaces): linked into libmpcg.so but kept
 # out of SOURCES / HEADERS, whose source_hash() is the identity the committed counter profiles
@@ -178,6 +178,20 @@ def build_fac_ab(name: str, force: bool = False) -> str:
     out = os.path.join(BUILD, "ab", name, "libmpcg.so")
     os.makedirs(os.path.dirname(out), exist_ok=True)
     return build_lib(force=force, extra_flags=FAC_AB[name], out=out,
+                     sources=("mpcg_kernels.hip", "mpcg_prepare.hip", "mpcg_inst_tmpc20.hip"))
+
+
+# the build without the level tickets that tests/test_gpu_tail_levels.py and the A/B runs compare the production
+# library with: the parent kernels.  `tail_poison` is the diagnostic build behind the carry set
+# (NaN in everything else at every SQP-RTI boundary); __graft_entry__.build() does not make it.
+TAIL_AB = {"tail_off": ["-DMPCG_TAIL_LEVELS=0"], "tail_poison": ["-DMPCG_LEVEL_POISON"]}
+
+
+def build_tail_ab(name: str = "tail_off", force: bool = False) -> str:
+    """build/ab/<name>/libmpcg.so: libmpcg.so with TAIL_AB[name]'s switches, instances of mpcg_inst_tmpc20.hip only"""
+    out = os.path.join(BUILD, "ab", name, "libmpcg.so")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    return build_lib(force=force, extra_flags=TAIL_AB[name], out=out,
                      sources=("mpcg_kernels.hip", "mpcg_prepare.hip", "mpcg_inst_tmpc20.hip"))
 
 

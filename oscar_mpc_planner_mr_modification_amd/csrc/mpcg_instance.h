@@ -35,6 +35,8 @@ int mpcg_register_instance(int abi_version, int model, int N, int n_lin, int n_e
                            int qp_mem_size, long long workspace_bytes_per_solve, const char* traits);
 /* instance registrations refused for another ABI since libmpcg.so loaded */
 int mpcg_rejected_instances(void);
+/* the K that mpcg_debug_set_tail_levels (mpcg.h, tests only) forces on `stream`'s launches, or -1 */
+int mpcg_debug_tail_levels(void* stream);
 }
 /* the work-queue words at the head of an instance workspace (sqp_kernel) */
 #define MPCG_QUEUE_BYTES 256
@@ -43,7 +45,7 @@ namespace mpcg {
 
 // grid of a work-queue launch: the workgroups the stream's device holds at once (occupancy x
 // CUs), at most one per problem; cached per device.
-template <class C, bool FULL, int PROF>
+template <class C, bool FULL, int PROF, int TAILK = 0>
 int queue_grid(int batch, hipStream_t stream) {
     constexpr int MAXDEV = 64;
     static std::atomic<int> resident[MAXDEV];  // 0: not yet asked, -1: no answer
@@ -57,8 +59,12 @@ int queue_grid(int batch, hipStream_t stream) {
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0) {
             int cur = 0;
             const bool sw = hipGetDevice(&cur) == hipSuccess && cur != dev && hipSetDevice(dev) == hipSuccess;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, sqp_kernel<C, FULL, PROF>, 64, 0) != hipSuccess)
-                per_cu = 0;
+            hipError_t e;
+            if constexpr (TAILK != 0)
+                e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, sqp_kernel<C, FULL, PROF, TAILK>, 64, 0);
+            else
+                e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, sqp_kernel<C, FULL, PROF>, 64, 0);
+            if (e != hipSuccess) per_cu = 0;
             if (sw) (void)hipSetDevice(cur);
             if (per_cu > 0) r = per_cu * cus;
         }
@@ -73,6 +79,36 @@ void launch_kernel(const mpcg_problem* pr, int batch, const mpcg_io* io, hipStre
                    double* gws, unsigned* queue) {
     hipLaunchKernelGGL((sqp_kernel<C, FULL, PROF>), dim3(queue ? queue_grid<C, FULL, PROF>(batch, st) : batch),
                        dim3(64), 0, st, *pr, batch, *io, stamps, gws, queue);
+}
+
+// TAIL_LEVELS: how many resident grids of solves at the end of a work-queue launch are taken one SQP-RTI
+// iteration per ticket (the schedule model's robust choice, confirmed by the A/B on C2, C1)
+#ifndef MPCG_TAIL_K_GRIDS
+#define MPCG_TAIL_K_GRIDS 3
+#endif
+
+// the lean work-queue launch of a TAIL_LEVELS instance (sqp_kernel<C, false, PROF, 1>): K from tail::plan_k
+// -- the default multiple of the grid, or what mpcg_debug_set_tail_levels forces on the stream --, its
+// boundary words zeroed on the stream next to the queue words
+template <class C, int PROF>
+int launch_tail(const mpcg_problem* pr, int batch, const mpcg_io* io, hipStream_t st, unsigned long long* stamps,
+                double* gws, unsigned* queue) {
+    const int grid = queue ? queue_grid<C, false, PROF, 1>(batch, st) : batch;
+    int k = 0;
+    if (queue) {
+        const int forced = mpcg_debug_tail_levels((void*)st);
+        k = tail::plan_k(batch, grid, pr->sqp_iters, forced >= 0 ? forced : MPCG_TAIL_K_GRIDS * grid);
+#ifdef MPCG_STAMPS
+        // the stamped build sums a solve's phase cycles on one wave and stores them at the solve's end: whole solves only
+        k = 0;
+#endif
+        if (k > 0 && hipMemsetAsync(gws + (size_t)batch * slot_doubles<C>(), 0,
+                                    (size_t)k * tail::WORDS_PER_SOLVE * sizeof(unsigned), st) != hipSuccess)
+            return (int)hipGetLastError();
+    }
+    hipLaunchKernelGGL((sqp_kernel<C, false, PROF, 1>), dim3(grid), dim3(64), 0, st, *pr, batch, *io, stamps, gws,
+                       queue, k);
+    return (int)hipGetLastError();
 }
 
 template <class C>
@@ -97,12 +133,16 @@ int launch_instance(const mpcg_problem* pr, int batch, const mpcg_io* io, void* 
     // memory, residuals or warm start the full variant runs the lean variant's operations)
     const int prof = qp_profile_kind(*pr);
     const bool full = io->stats || io->qp_in || io->qp_out || needs_full(*pr) || prof == PROF_RUNTIME;
-    if (full)
+    if (full) {
         launch_kernel<C, true, PROF_RUNTIME>(pr, batch, io, st, stamps, gws, queue);
-    else if (prof == PROF_HPIPM)
-        launch_kernel<C, false, PROF_HPIPM>(pr, batch, io, st, stamps, gws, queue);
-    else
+    } else if (prof == PROF_HPIPM) {
+        // the level tickets on HPIPM's profile only: the robust profile's shorter solves do not pay for the
+        // hand-overs at the same K (C1 +2.2 %, C2 -0.2 %), so its kernels keep the loop of §3.7
+        if constexpr (tail_levels<C>()) return launch_tail<C, PROF_HPIPM>(pr, batch, io, st, stamps, gws, queue);
+        else launch_kernel<C, false, PROF_HPIPM>(pr, batch, io, st, stamps, gws, queue);
+    } else {
         launch_kernel<C, false, PROF_ROBUST>(pr, batch, io, st, stamps, gws, queue);
+    }
     return (int)hipGetLastError();
 }
 

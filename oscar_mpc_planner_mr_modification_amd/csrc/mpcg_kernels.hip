@@ -284,6 +284,34 @@ int mpcg_debug_set_queue(void* stream, unsigned value) {
     return -1;
 }
 
+/* tests only (tests/test_gpu_tail_levels.py): the K of the level tickets forced per stream (include/mpcg.h),
+ * read by launch_tail (mpcg_instance.h) */
+static std::mutex g_tail_mutex;
+static std::vector<std::pair<void*, int>> g_tail_forced;
+static std::atomic<int> g_tail_forced_n{0};  // entries of g_tail_forced: a launch takes the lock only when a test forced a K
+
+int mpcg_debug_set_tail_levels(void* stream, int k) {
+    std::lock_guard<std::mutex> l(g_tail_mutex);
+    for (size_t e = 0; e < g_tail_forced.size(); ++e)
+        if (g_tail_forced[e].first == stream) {
+            if (k < 0) g_tail_forced.erase(g_tail_forced.begin() + (long)e);
+            else g_tail_forced[e].second = k;
+            g_tail_forced_n.store((int)g_tail_forced.size());
+            return 0;
+        }
+    if (k >= 0) g_tail_forced.emplace_back(stream, k);
+    g_tail_forced_n.store((int)g_tail_forced.size());
+    return 0;
+}
+
+int mpcg_debug_tail_levels(void* stream) {
+    if (g_tail_forced_n.load(std::memory_order_acquire) == 0) return -1;
+    std::lock_guard<std::mutex> l(g_tail_mutex);
+    for (const auto& e : g_tail_forced)
+        if (e.first == stream) return e.second;
+    return -1;
+}
+
 /* diagnostic builds only: device buffer of batch x 20 u64 phase-cycle sums */
 void mpcg_debug_set_stamp_buffer(unsigned long long* dev_ptr) { mpcg::g_stamps = dev_ptr; }
 

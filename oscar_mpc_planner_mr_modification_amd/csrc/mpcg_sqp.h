@@ -30,6 +30,7 @@
 #include "mpcg.h"
 #include "mpcg_bicycle.h"
 #include "mpcg_device.h"
+#include "mpcg_tail.h"
 
 namespace mpcg {
 
@@ -367,10 +368,34 @@ template <class C>
 __host__ __device__ constexpr size_t itref_doubles() {
     return 2 * (size_t)(C::N + 1) * C::NZ + (size_t)C::N * C::NX;
 }
-// one solve's global workspace: the GFH blocks, then the refinement scratch
+// one workgroup's slot of the global workspace: the GFH blocks, then the refinement scratch
+template <class C>
+__host__ __device__ constexpr size_t slot_doubles() {
+    return gfh_doubles<C>() + itref_doubles<C>();
+}
+// TAIL_LEVELS: the last solves of a work-queue launch run one SQP-RTI iteration per ticket (mpcg_tail.h,
+// DESIGN.md §3.12): the lean kernels of the queue instances with the split residual passes (C1, C2, the N 10
+// shape).  -DMPCG_TAIL_LEVELS=0 compiles the kernels without it (A/B and the bit comparison).
+#ifndef MPCG_TAIL_LEVELS
+#define MPCG_TAIL_LEVELS 1
+#endif
+template <class C>
+__host__ __device__ constexpr bool tail_levels() {
+    return MPCG_TAIL_LEVELS > 0 && C::QUEUE && !C::COMPACT && 2 * C::NB <= C::NZ && C::PARTS == 3 && C::NX == 5 &&
+           !lds_lean<C>() && !lds_gfh<C>();
+}
+// what a solve carries from one SQP-RTI iteration to the next (the lean kernels): the counters (8 doubles),
+// the iterate z, the dynamics multipliers, the initial state (padded to 8) and every lane's h-row multipliers
+template <class C>
+__host__ __device__ constexpr size_t carry_doubles() {
+    return tail_levels<C>() ? 8 + (size_t)(C::N + 1) * C::NZ + (size_t)C::N * C::NX + 8 + 64 * (size_t)C::HS : 0;
+}
+// one solve's share of the global workspace: a workgroup slot and, with TAIL_LEVELS, the solve's boundary
+// words and carry block.  A launch of `batch` solves lays them out as batch slots (the first grid of them
+// used), then the words of the tail solves, then their carry blocks
 template <class C>
 __host__ __device__ constexpr size_t ws_doubles() {
-    return gfh_doubles<C>() + itref_doubles<C>();
+    return slot_doubles<C>() + (tail_levels<C>() ? tail::WORDS_PER_SOLVE / 2 + carry_doubles<C>() : 0);
 }
 
 // Diagnostic per-phase cycle stamps (separate build with -DMPCG_STAMPS; the
@@ -627,11 +652,54 @@ __host__ __device__ inline int qp_profile_kind(const mpcg_problem& pr) {
 #else
 #define MPCG_KERNEL_ATTR __launch_bounds__(64, 1)
 #endif
-// one solve `sol` on the calling wavefront (the body of sqp_kernel)
-template <class C, bool FULL, int PROF>
+// the boundary words' atomic operation on the device (mpcg_tail.h): one fetch-add at agent scope, which
+// releases the wave's earlier stores and acquires for its later loads across the XCDs' L2s
+struct TailDeviceAtomic {
+    __host__ __device__ static unsigned fetch_add(unsigned* p, unsigned v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        return __hip_atomic_fetch_add(p, v, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+#else
+        const unsigned o = *p;
+        *p = o + v;
+        return o;
+#endif
+    }
+};
+// what a level ticket tells the solve body (TAIL kernels): the level to start at, whether the solve is handed
+// on level by level, and the tail solve's boundary words and carry block
+struct TailCtl {
+    int cj = 0;             // 0: the whole solve; j + 1: one level of tail solve j
+    int lvl = 0;            // the level (SQP-RTI iteration) to run
+    bool in_place = false;  // lvl > 0 on the wave that ran lvl - 1: the solve's LDS image is still here
+};
+// The carry block of a tail solve (carry_doubles): [3] the QP iterations so far, [8..] z, then the dynamics
+// multipliers, the initial state (8 doubles) and the lanes' h-row multipliers [HS][64].  tail_save writes it at
+// a level's end; the solve body reads it at the next level's start.
+template <int HS>
+struct TailNlam {
+    double v[HS];
+};
+template <int HS>
+__device__ __attribute__((noinline)) void tail_save(double* cy, int lane, TailNlam<HS> nl, const double* z, int nz,
+                                                    const double* pi, int npi, const double* xi, int nxi, int qp_total) {
+    double* o = cy + 8;
+    for (int e = lane; e < nz; e += 64) o[e] = z[e];
+    o += nz;
+    for (int e = lane; e < npi; e += 64) o[e] = pi[e];
+    o += npi;
+    if (lane < nxi) o[lane] = xi[lane];
+    o += 8;
+#pragma unroll
+    for (int r = 0; r < HS; ++r) o[r * 64 + lane] = nl.v[r];
+    if (lane == 0) cy[3] = qp_total;
+}
+// one solve `sol` on the calling wavefront (the body of sqp_kernel).  TAIL with tc.cj: level tc.lvl of it;
+// tail_more comes back as the count of levels done when the level was saved to the carry block and the
+// solve goes on, else 0
+template <class C, bool FULL, int PROF, bool TAIL = false>
 __device__ __forceinline__ void sqp_solve(mpcg_problem pr, int batch, mpcg_io io,
                                           unsigned long long* __restrict__ stamps, double* __restrict__ gws,
-                                          const int sol) {
+                                          const int sol, const TailCtl tc, int& tail_more) {
 #include "mpcg_sqp_body.inc"
 }
 
@@ -651,6 +719,9 @@ __global__ MPCG_KERNEL_ATTR void sqp_kernel(mpcg_problem pr, int batch, mpcg_io 
     if constexpr (!C::QUEUE) {
         (void)queue;
         const int sol = blockIdx.x;
+        constexpr bool TAIL = false;
+        constexpr TailCtl tc{};
+        [[maybe_unused]] int tail_more = 0;
 #include "mpcg_sqp_body.inc"
     } else {
         if (blockDim.x != 64) {
@@ -669,8 +740,75 @@ __global__ MPCG_KERNEL_ATTR void sqp_kernel(mpcg_problem pr, int batch, mpcg_io 
             return t < (unsigned)batch ? (int)t : batch;
         };
         for (int sol = q ? next() : (int)blockIdx.x; sol < batch; sol = q ? next() : batch) {
-            sqp_solve<C, FULL, PROF>(pr, batch, io, stamps, gws, sol);
+            int more = 0;
+            sqp_solve<C, FULL, PROF>(pr, batch, io, stamps, gws, sol, TailCtl{}, more);
             wave_sync();
+        }
+    }
+}
+
+// The lean work-queue launch of the TAIL_LEVELS instances (tail_levels<C>()): as above, but the last tail_k
+// solves of the batch are taken one SQP-RTI iteration per ticket (mpcg_tail.h: the ticket numbering and the
+// boundary words' protocol).  words: tail_k x tail::WORDS_PER_SOLVE boundary words, zeroed on the stream
+// before the launch; carry: tail_k carry blocks of carry_doubles<C>().  tail_k == 0 (launch_instance: a batch
+// that fits the grid, more levels than the words hold) is the launch above.  No wave ever waits for another:
+// a level whose predecessor has not finished is left to the predecessor's wave.
+template <class C, bool FULL, int PROF, int TAILK>
+__global__ MPCG_KERNEL_ATTR void sqp_kernel(mpcg_problem pr, int batch, mpcg_io io,
+                                                    unsigned long long* __restrict__ stamps,
+                                                    double* __restrict__ gws, unsigned* __restrict__ queue, int tail_k) {
+    static_assert(TAILK == 1 && !FULL && tail_levels<C>(), "the lean kernels of the TAIL_LEVELS instances only");
+    if (blockDim.x != 64) {
+        if (threadIdx.x == 0)
+            for (int sol = blockIdx.x; sol < batch; sol += gridDim.x) io.exit_code[sol] = -1;
+        return;
+    }
+    const bool q = queue != nullptr;  // (NULL: workgroup b solves problem b, whole)
+    // (few uniform values live across the solve body, whose scalar registers are spilled to vector lanes as it
+    // is: the words and carry blocks are addressed again from the arguments where they are used)
+    auto words = [&]() { return (unsigned*)(gws + (size_t)batch * slot_doubles<C>()); };
+    int sol = (int)blockIdx.x;
+    int next_lvl = 0;  // > 0: this wave goes on in place with that level of `sol`
+    // (one call site of the solve body: whole solves, level tickets and levels continued in place)
+    for (;;) {
+        TailCtl tc;
+        if (next_lvl > 0) {
+            tc.lvl = next_lvl;
+            tc.cj = sol - (batch - tail_k) + 1;
+            tc.in_place = true;
+        } else if (q) {
+            unsigned t = 0;
+            if (threadIdx.x == 0) t = atomicAdd(&queue[0], 1u);
+            t = __builtin_amdgcn_readfirstlane(t);
+            const tail::Ticket tk = tail::decode(tail::Plan{batch, tail_k, pr.sqp_iters}, t);
+            if (tk.kind == tail::END) break;
+            sol = tk.sol;
+            if (tk.kind == tail::LEVEL) {
+                const int j = tk.sol - (batch - tail_k);
+                unsigned mine = 0;
+                if (threadIdx.x == 0) mine = tail::claim<TailDeviceAtomic>(words(), j, tk.lvl) ? 1u : 0u;
+                // first at the boundary, or the solve has ended: nothing to do for this ticket
+                if (!__builtin_amdgcn_readfirstlane(mine)) continue;
+                // the carry block's loads come after the claim and see its writer's stores
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+                tc.lvl = tk.lvl;
+                tc.cj = j + 1;
+            }
+        }
+        int more = 0;
+        sqp_solve<C, FULL, PROF, true>(pr, batch, io, stamps, gws, sol, tc, more);
+        wave_sync();
+        if (!q) break;
+        next_lvl = 0;
+        if (more > 0) {
+            // level more - 1 is saved and the solve goes on: every lane's stores of the carry block are visible
+            // device-wide before the word moves.  Second at the word (the next level's ticket has fallen
+            // through): this wave runs that level too; first: the ticket's holder will load the block
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+            unsigned go_on = 0;
+            if (threadIdx.x == 0)
+                go_on = tail::finish<TailDeviceAtomic>(words(), sol - (batch - tail_k), more - 1) ? 1u : 0u;
+            if (__builtin_amdgcn_readfirstlane(go_on)) next_lvl = more;
         }
     }
 }

@@ -80,7 +80,7 @@
     // slot is the workgroup's: one solve at a time runs on a workgroup and rewrites its slot before reading
     // it (the blocks per linearisation, the refinement scratch per refinement), so a work-queue launch
     // needs grid slots, not batch (mpcg_instance.h launch_instance)
-    double* const gsol = gws + (size_t)(int)blockIdx.x * ws_doubles<C>();  // this workgroup's workspace
+    double* const gsol = gws + (size_t)(int)blockIdx.x * slot_doubles<C>();  // this workgroup's workspace
     double* const gF = GFH ? gsol : nullptr;
     // the iterative refinement's scratch (rare path): unrefined step, its multipliers, dynamics rhs
     double* const g_ddz0 = gsol + gfh_doubles<C>();
@@ -195,6 +195,41 @@
     // are the bits the residual pass would compute from the stored iterate
     auto stepped = [](double x, double a, double dx) -> double { return x + a * dx; };
     Rows<C> R;
+    // TAIL (mpcg_tail.h): a level ticket past the solve's first starts from the solve's carry block -- what
+    // crosses an SQP-RTI boundary of the lean kernel: the iterate, the dynamics multipliers, the initial state,
+    // every lane's h-row multipliers and the counters below -- instead of the warm start
+    constexpr int CY_Z = 8, CY_PI = CY_Z + (N + 1) * NZ, CY_XI = CY_PI + N * NX, CY_NLAM = CY_XI + 8;
+    // (the block's address waits in LDS for the save at the level's end -- S.Hst is unused without GFH --:
+    // kept in scalar registers across the level, it and the arguments it comes from cost the C2 kernel its
+    // scratch-free allocation, 0 -> 20 B/lane)
+    [[maybe_unused]] const bool by_levels = tc.cj > 0;
+    if constexpr (TAIL) {
+        static_assert(!GFH, "S.Hst holds the carry block's address: the GFH storage uses it for the stage blocks");
+        if (by_levels && lane == 0)
+            S.Hst[0] = __builtin_bit_cast(double, gws + (size_t)batch * (slot_doubles<C>() + tail::WORDS_PER_SOLVE / 2) +
+                                                      (size_t)(tc.cj - 1) * carry_doubles<C>());
+        wave_sync();
+    }
+    [[maybe_unused]] auto carry_block = [&]() -> double* { return __builtin_bit_cast(double*, S.Hst[0]); };
+    [[maybe_unused]] bool resumed = false;
+    if constexpr (TAIL) resumed = tc.lvl > 0;
+    if constexpr (TAIL) {
+        if (resumed) {
+            const double* cy = carry_block();
+#pragma unroll
+            for (int r = 0; r < HS; ++r) R.nlam[r] = cy[CY_NLAM + r * 64 + lane];
+            // (a wave that goes on with the level it has just saved still holds the solve's LDS image)
+            if (!tc.in_place) {
+                for (int e = lane; e < (N + 1) * NZ; e += 64) (&S.z[0][0])[e] = cy[CY_Z + e];
+                for (int e = lane; e < N * NX; e += 64) (&S.pi_nlp[0][0])[e] = cy[CY_PI + e];
+                if (lane < NX) S.xinit[lane] = cy[CY_XI + lane];
+                for (int e = lane; e <= N; e += 64) S.dH[e][C::NDH - 1] = 0.0;
+            }
+        }
+    }
+    // (the warm start stands twice: the kernels without level tickets run it unconditionally, with no branch in
+    // front of it that would reorder their blocks -- they compile to the instructions they had before)
+    if constexpr (!TAIL) {
 #pragma unroll
     for (int r = 0; r < HS; ++r)
         R.nlam[r] = (lam_in && LR.h_on(r)) ? lam_in[(size_t)k * LAMS + NX + LR.hrow(r)] : 0.0;
@@ -206,6 +241,19 @@
         (&S.pi_nlp[0][0])[e] = lam_in ? lam_in[(size_t)(e / NX) * LAMS + e % NX] : 0.0;
     if (lane < NX) S.xinit[lane] = io.xinit[(size_t)sol * NX + lane];
     for (int e = lane; e <= N; e += 64) S.dH[e][C::NDH - 1] = 0.0;
+    } else if (!resumed) {
+#pragma unroll
+    for (int r = 0; r < HS; ++r)
+        R.nlam[r] = (lam_in && LR.h_on(r)) ? lam_in[(size_t)k * LAMS + NX + LR.hrow(r)] : 0.0;
+
+    // ---- load warm start (loadWarmstart, acados_solver_interface.cpp:274-284)
+    const double* w = io.warm + (size_t)sol * (N + 1) * NZ;
+    for (int e = lane; e < (N + 1) * NZ; e += 64) (&S.z[0][0])[e] = w[e];
+    for (int e = lane; e < N * NX; e += 64)
+        (&S.pi_nlp[0][0])[e] = lam_in ? lam_in[(size_t)(e / NX) * LAMS + e % NX] : 0.0;
+    if (lane < NX) S.xinit[lane] = io.xinit[(size_t)sol * NX + lane];
+    for (int e = lane; e <= N; e += 64) S.dH[e][C::NDH - 1] = 0.0;
+    }
     // the capsule's QP memory, if any: the previous QP's solution, whose row multipliers are
     // also the NLP's (FIXED_STEP) -- read by the NLP residuals -- and, with the HPIPM warm
     // start (qp_solver_warm_start 2), the initial point of the first QP; the later QPs
@@ -250,8 +298,45 @@
     double res_eq = 0.0;
     double nlp_stat = 0.0, nlp_ineq = 0.0, nlp_comp = 0.0;  // NLP residuals of the last linearisation
     bool nlp_nonfinite = false;
+    int it0 = 0;
+    if constexpr (TAIL) {
+        if (resumed) {
+            // the counters of the levels before.  A solve that goes on past a level has run one QP per level,
+            // each of them successful (any other QP status ends an SQP-RTI solve), so sqp_iter is the level and
+            // n_maxit 0; acados_status, qp_status and res_eq are rewritten by the level before they are read.
+            // Only the QP iteration count comes from the block (uniform: every lane reads the same word)
+            it0 = sqp_iter = tc.lvl;
+            qp_total = __builtin_amdgcn_readfirstlane((int)carry_block()[3]);
+        }
+    }
 
-    for (int it = 0; sqp_mode || it < pr.sqp_iters; ++it) {
+    for (int it = it0; sqp_mode || it < pr.sqp_iters; ++it) {
+#ifdef MPCG_LEVEL_POISON
+        // diagnostic build only (DESIGN.md §3.12): every SQP-RTI iteration of a lean solve after its first starts
+        // with NaN in every LDS array and row register that is not in the carry block, so that a value which
+        // reaches an iteration only from the one before on the same wave shows in the outputs
+        if (!FULL && it > 0) {
+            wave_sync();
+            const double* const lds0 = (const double*)&S;
+            auto within = [&](const void* a, size_t bytes, const double* p) {
+                return (const char*)p >= (const char*)a && (const char*)p < (const char*)a + bytes;
+            };
+            for (int e = lane; e < (int)(sizeof(S) / 8); e += 64) {
+                const double* p = lds0 + e;
+                if (within(&S.z, sizeof S.z, p) || within(&S.pi_nlp, sizeof S.pi_nlp, p) ||
+                    within(&S.xinit, sizeof S.xinit, p) || within(&S.Hst, sizeof S.Hst, p))
+                    continue;
+                const bool zero_slot = within(&S.dH, sizeof S.dH, p) && (int)(p - &S.dH[0][0]) % C::NDH == C::NDH - 1;
+                ((double*)&S)[e] = zero_slot ? 0.0 : __builtin_nan("");
+            }
+#pragma unroll
+            for (int s = 0; s < C::SLOTS; ++s) {
+                R.t[s] = R.l[s] = R.rin[s] = R.pr[s] = __builtin_nan("");
+                R.set_it(s, __builtin_nan(""));
+            }
+            wave_sync();
+        }
+#endif
         // parameter loads are re-issued where they are used rather than hoisted out of
         // the SQP / QP loops into registers that stay live (and spill) across them
         if constexpr (C::RELOAD_PARAMS) asm volatile("" : "+v"(pk));
@@ -2334,6 +2419,25 @@
         // SQP-RTI: the reference's loop stops after a QP that did not succeed
         // (acados_solver_interface.cpp:105); a full SQP call continues after a max-iter QP
         if (!sqp_mode && qstat != AC_SUCCESS) break;
+        if constexpr (TAIL) {
+            // a solve handed on by levels runs one SQP-RTI iteration per call
+            if (by_levels) break;
+        }
+    }
+    if constexpr (TAIL) {
+        // a solve handed on by levels whose level ended without ending the solve (every exit of the loop that
+        // ends the solve leaves another QP status): save what the next level starts from and leave; the
+        // kernel's ticket loop meets the next level's ticket at the boundary word
+        if (by_levels && qp_status == AC_SUCCESS && sqp_iter < pr.sqp_iters) {
+            // (a call, not inline: the copies' own registers stay out of the solve's allocation)
+            TailNlam<HS> nl;
+#pragma unroll
+            for (int r = 0; r < HS; ++r) nl.v[r] = R.nlam[r];
+            tail_save<HS>(carry_block(), lane, nl, &S.z[0][0], (N + 1) * NZ, &S.pi_nlp[0][0], N * NX, &S.xinit[0], NX,
+                          qp_total);
+            tail_more = sqp_iter;
+            return;
+        }
     }
 
     // ---- completeOneIteration (acados_solver_interface.cpp:162-204)

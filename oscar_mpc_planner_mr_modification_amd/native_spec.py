@@ -266,6 +266,7 @@ def _signatures() -> dict:
             "mpcg_select_lowest_cost_device": (i, [i, i, vp, vp, vp, vp]),
             "mpcg_winner_records_device": (i, [i, i, i, i, i] + [vp] * 6),
             "mpcg_release_stream_workspace": (i, [vp]),
+            "mpcg_debug_set_tail_levels": (i, [vp, i]),
             "mpcg_instance_traits": (i, [P, C.c_char_p, i]),
             "mpcg_problem_set_qp_profile": (i, [P, i]),
         },

@@ -8,7 +8,8 @@ Compiles the built-in instance families of both trees with the library's flags p
 `--cuda-device-only -S` (or reuses `<family>.s` files: --old-asm / --new-asm DIR), replaces every
 sqp_kernel symbol by `sqp_kernel<Cfg<...>,FULL,PROF>` -- so a template parameter or kernel argument
 added or removed after those three does not show as a renamed symbol -- and compares, per kernel,
-the instruction stream, the kernel descriptor and the argument metadata.
+the instruction stream, the kernel descriptor and the argument metadata.  Basic-block labels are
+compared without the function's ordinal in the unit (`.LBB<ordinal>_<block>`).
 
 Differences are sorted into classes:
   cuid            the per-translation-unit __hip_cuid_* symbol (always permitted)
@@ -101,7 +102,9 @@ def parse(path: str) -> dict:
             name, code = m.group(1), []
             i += 1
             while i < n and not lines[i].startswith("\t.section") and not lines[i].startswith(".Lfunc_end"):
-                s = strip(lines[i])
+                # (block labels carry the function's ordinal in its translation unit, .LBB<ordinal>_<block>: a
+                # kernel added to or removed from the unit renumbers every later kernel's labels)
+                s = re.sub(r"\.L(BB|JTI)\d+_", r".L\1_", strip(lines[i]))
                 if s:
                     code.append(s)
                 used.add(i)
