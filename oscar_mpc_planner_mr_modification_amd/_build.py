@@ -184,7 +184,13 @@ def build_fac_ab(name: str, force: bool = False) -> str:
 # the build without the level tickets that tests/test_gpu_tail_levels.py and the A/B runs compare the production
 # library with: the parent kernels.  `tail_poison` is the diagnostic build behind the carry set
 # (NaN in everything else at every SQP-RTI boundary); __graft_entry__.build() does not make it.
-TAIL_AB = {"tail_off": ["-DMPCG_TAIL_LEVELS=0"], "tail_poison": ["-DMPCG_LEVEL_POISON"]}
+# tail_g1 .. tail_g3: 1, 2 and 3 SQP-RTI iterations per level ticket (tests/test_gpu_tail_groups.py
+# holds each of them to tail_off bit for bit).  tail_fences0 is the hand-over of §3.12 (acquire-release fetch-adds
+# under explicit fences, one iteration per ticket): the A/B partner of the fence pair, not made by build().
+TAIL_GROUPS = (1, 2, 3)
+TAIL_AB = {"tail_off": ["-DMPCG_TAIL_LEVELS=0"], "tail_poison": ["-DMPCG_LEVEL_POISON"],
+           **{f"tail_g{g}": [f"-DMPCG_TAIL_GROUP={g}"] for g in TAIL_GROUPS},
+           "tail_fences0": ["-DMPCG_TAIL_FENCE_PAIR=0", "-DMPCG_TAIL_GROUP=1"]}
 
 
 def build_tail_ab(name: str = "tail_off", force: bool = False) -> str:

@@ -97,7 +97,9 @@ int launch_tail(const mpcg_problem* pr, int batch, const mpcg_io* io, hipStream_
     int k = 0;
     if (queue) {
         const int forced = mpcg_debug_tail_levels((void*)st);
-        k = tail::plan_k(batch, grid, pr->sqp_iters, forced >= 0 ? forced : MPCG_TAIL_K_GRIDS * grid);
+        // (the limits of plan_k are the boundary words', so they hold for the groups the kernel's tickets stand for)
+        k = tail::plan_k(batch, grid, tail::groups(pr->sqp_iters, MPCG_TAIL_GROUP),
+                         forced >= 0 ? forced : MPCG_TAIL_K_GRIDS * grid);
 #ifdef MPCG_STAMPS
         // the stamped build sums a solve's phase cycles on one wave and stores them at the solve's end: whole solves only
         k = 0;

@@ -379,6 +379,17 @@ __host__ __device__ constexpr size_t slot_doubles() {
 #ifndef MPCG_TAIL_LEVELS
 #define MPCG_TAIL_LEVELS 1
 #endif
+// the hand-over of a tail solve.  MPCG_TAIL_FENCE_PAIR: one release fence by the finisher and
+// one acquire fence by the ticket holder that takes the solve over, around relaxed fetch-adds on the boundary
+// word (0: acquire-release fetch-adds with the fences on top, as §3.12 shipped).  MPCG_TAIL_GROUP: the SQP-RTI
+// iterations per ticket after the first iteration (mpcg_tail.h; 1: one iteration per ticket)
+#ifndef MPCG_TAIL_FENCE_PAIR
+#define MPCG_TAIL_FENCE_PAIR 1
+#endif
+#ifndef MPCG_TAIL_GROUP
+#define MPCG_TAIL_GROUP 2
+#endif
+static_assert(MPCG_TAIL_GROUP >= 1, "MPCG_TAIL_GROUP: SQP-RTI iterations per ticket");
 template <class C>
 __host__ __device__ constexpr bool tail_levels() {
     return MPCG_TAIL_LEVELS > 0 && C::QUEUE && !C::COMPACT && 2 * C::NB <= C::NZ && C::PARTS == 3 && C::NX == 5 &&
@@ -652,12 +663,16 @@ __host__ __device__ inline int qp_profile_kind(const mpcg_problem& pr) {
 #else
 #define MPCG_KERNEL_ATTR __launch_bounds__(64, 1)
 #endif
-// the boundary words' atomic operation on the device (mpcg_tail.h): one fetch-add at agent scope, which
-// releases the wave's earlier stores and acquires for its later loads across the XCDs' L2s
+// the boundary words' atomic operation on the device (mpcg_tail.h): one relaxed fetch-add at agent scope.  It
+// orders nothing by itself: the ticket loop of sqp_kernel puts one release fence in front of the finisher's and
+// one acquire fence behind the ticket holder's that returned 1, and the two fences synchronise through the
+// read-modify-writes on the word.  A claim publishes nothing and a finish reads nothing of another wave, so
+// neither pays the other half (a write-back and an invalidate of the caches each)
 struct TailDeviceAtomic {
     __host__ __device__ static unsigned fetch_add(unsigned* p, unsigned v) {
 #if defined(__HIP_DEVICE_COMPILE__)
-        return __hip_atomic_fetch_add(p, v, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+        return __hip_atomic_fetch_add(p, v, MPCG_TAIL_FENCE_PAIR ? __ATOMIC_RELAXED : __ATOMIC_ACQ_REL,
+                                      __HIP_MEMORY_SCOPE_AGENT);
 #else
         const unsigned o = *p;
         *p = o + v;
@@ -748,9 +763,9 @@ __global__ MPCG_KERNEL_ATTR void sqp_kernel(mpcg_problem pr, int batch, mpcg_io 
 }
 
 // The lean work-queue launch of the TAIL_LEVELS instances (tail_levels<C>()): as above, but the last tail_k
-// solves of the batch are taken one SQP-RTI iteration per ticket (mpcg_tail.h: the ticket numbering and the
-// boundary words' protocol).  words: tail_k x tail::WORDS_PER_SOLVE boundary words, zeroed on the stream
-// before the launch; carry: tail_k carry blocks of carry_doubles<C>().  tail_k == 0 (launch_instance: a batch
+// solves of the batch are taken one group of SQP-RTI iterations per ticket -- iteration 0, then MPCG_TAIL_GROUP
+// iterations each -- (mpcg_tail.h: the groups, the ticket numbering and the boundary words' protocol).  words:
+// tail_k x tail::WORDS_PER_SOLVE boundary words, zeroed on the stream before the launch; carry: tail_k carry blocks of carry_doubles<C>().  tail_k == 0 (launch_instance: a batch
 // that fits the grid, more levels than the words hold) is the launch above.  No wave ever waits for another:
 // a level whose predecessor has not finished is left to the predecessor's wave.
 template <class C, bool FULL, int PROF, int TAILK>
@@ -764,6 +779,7 @@ __global__ MPCG_KERNEL_ATTR void sqp_kernel(mpcg_problem pr, int batch, mpcg_io 
         return;
     }
     const bool q = queue != nullptr;  // (NULL: workgroup b solves problem b, whole)
+    constexpr int G = MPCG_TAIL_GROUP;
     // (few uniform values live across the solve body, whose scalar registers are spilled to vector lanes as it
     // is: the words and carry blocks are addressed again from the arguments where they are used)
     auto words = [&]() { return (unsigned*)(gws + (size_t)batch * slot_doubles<C>()); };
@@ -780,18 +796,21 @@ __global__ MPCG_KERNEL_ATTR void sqp_kernel(mpcg_problem pr, int batch, mpcg_io 
             unsigned t = 0;
             if (threadIdx.x == 0) t = atomicAdd(&queue[0], 1u);
             t = __builtin_amdgcn_readfirstlane(t);
-            const tail::Ticket tk = tail::decode(tail::Plan{batch, tail_k, pr.sqp_iters}, t);
+            // (a level ticket stands for a group of SQP-RTI iterations: tk.lvl is the group)
+            const tail::Ticket tk = tail::decode(tail::Plan{batch, tail_k, tail::groups(pr.sqp_iters, G)}, t);
             if (tk.kind == tail::END) break;
             sol = tk.sol;
             if (tk.kind == tail::LEVEL) {
                 const int j = tk.sol - (batch - tail_k);
                 unsigned mine = 0;
                 if (threadIdx.x == 0) mine = tail::claim<TailDeviceAtomic>(words(), j, tk.lvl) ? 1u : 0u;
-                // first at the boundary, or the solve has ended: nothing to do for this ticket
+                // first at the boundary, or the solve has ended: nothing to do for this ticket, and no cache
+                // operation either
                 if (!__builtin_amdgcn_readfirstlane(mine)) continue;
-                // the carry block's loads come after the claim and see its writer's stores
+                // the hand-over's one acquire: the carry block's loads come after the claim that met the
+                // finisher's add and see what the finisher's release fence made visible
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                tc.lvl = tk.lvl;
+                tc.lvl = tail::group_first(tk.lvl, G);
                 tc.cj = j + 1;
             }
         }
@@ -801,13 +820,19 @@ __global__ MPCG_KERNEL_ATTR void sqp_kernel(mpcg_problem pr, int batch, mpcg_io 
         if (!q) break;
         next_lvl = 0;
         if (more > 0) {
-            // level more - 1 is saved and the solve goes on: every lane's stores of the carry block are visible
-            // device-wide before the word moves.  Second at the word (the next level's ticket has fallen
-            // through): this wave runs that level too; first: the ticket's holder will load the block
+            // the group that ends with level more - 1 is saved and the solve goes on: every lane's stores of the
+            // carry block are visible device-wide before the word moves.  Second at the word (the next group's
+            // ticket has fallen through): this wave runs that group too; first: the ticket's holder will load
+            // the block.  The hand-over's one release: the fence writes the block back, and the wait stands
+            // here in so many words -- the compiler drops a release's own wait where it can prove the wave's
+            // counters empty, and the relaxed add behind it brings none
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+#if MPCG_TAIL_FENCE_PAIR
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#endif
             unsigned go_on = 0;
             if (threadIdx.x == 0)
-                go_on = tail::finish<TailDeviceAtomic>(words(), sol - (batch - tail_k), more - 1) ? 1u : 0u;
+                go_on = tail::finish<TailDeviceAtomic>(words(), sol - (batch - tail_k), tail::group_of(more - 1, G)) ? 1u : 0u;
             if (__builtin_amdgcn_readfirstlane(go_on)) next_lvl = more;
         }
     }

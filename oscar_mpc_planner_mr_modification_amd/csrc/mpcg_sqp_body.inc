@@ -2420,8 +2420,10 @@
         // (acados_solver_interface.cpp:105); a full SQP call continues after a max-iter QP
         if (!sqp_mode && qstat != AC_SUCCESS) break;
         if constexpr (TAIL) {
-            // a solve handed on by levels runs one SQP-RTI iteration per call
-            if (by_levels) break;
+            // a solve handed on by levels leaves after its group's last SQP-RTI iteration (mpcg_tail.h: iteration
+            // 0, then MPCG_TAIL_GROUP iterations per call -- a test of `it` against a constant, no value kept
+            // across the body for it; always true at one iteration per group)
+            if (by_levels && tail::group_ends(it, MPCG_TAIL_GROUP)) break;
         }
     }
     if constexpr (TAIL) {

@@ -9,6 +9,12 @@
 //   D + l K + j       level l of solve D + j  (level-major: every level 0 before any level 1)
 //   >= D + L K        the wave leaves the loop
 //
+// Grouped levels: a ticket may stand for a group of consecutive SQP-RTI iterations instead of
+// one -- group 0 is iteration 0 alone (its QP is the long one), then groups of G iterations, the last one
+// possibly short (groups, group_first, group_of below).  Everything in this header then reads "group" for
+// "level": Plan.L is the number of groups, Ticket.lvl the group, and a boundary word stands between two
+// groups.  G = 1 is one iteration per ticket.
+//
 // Between level l and level l + 1 of a tail solve stands one boundary word, zero at launch.  Exactly two
 // parties may add one to it: the wave that finished level l (after it saved the solve's carry block) and the
 // wave that drew the ticket of level l + 1 (before it loads the block).  Whoever arrives second runs level
@@ -37,7 +43,7 @@ constexpr int WORDS_PER_SOLVE = 16;
 struct Plan {
     int batch;  // solves of the launch
     int K;      // the last K of them by levels (0: none)
-    int L;      // levels per solve (pr.sqp_iters)
+    int L;      // levels per solve (groups(pr.sqp_iters, G))
 };
 
 enum Kind { WHOLE = 0, LEVEL = 1, END = 2 };
@@ -46,6 +52,14 @@ struct Ticket {
     int sol;  // solve (WHOLE, LEVEL)
     int lvl;  // level (LEVEL)
 };
+
+// The groups of a solve of `iters` SQP-RTI iterations at G iterations per group after iteration 0, the first
+// iteration of group g and the group that iteration `it` belongs to
+MPCG_TAIL_HD constexpr int groups(int iters, int G) { return iters <= 1 ? iters : 1 + (iters - 2 + G) / G; }
+MPCG_TAIL_HD constexpr int group_first(int g, int G) { return g <= 0 ? 0 : 1 + (g - 1) * G; }
+MPCG_TAIL_HD constexpr int group_of(int it, int G) { return it <= 0 ? 0 : 1 + (it - 1) / G; }
+// iteration `it` is the last of its group (of a group that is not cut short by the solve's end)
+MPCG_TAIL_HD constexpr bool group_ends(int it, int G) { return it % G == 0; }
 
 // K of a launch: none when the queue does not wrap (batch <= grid), when the solve has more levels than the
 // words hold or fewer than two, else `want` clamped to the batch

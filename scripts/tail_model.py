@@ -1,7 +1,12 @@
 """Schedule model of the work-queue launch with level tickets (CPU only).
 
-    python scripts/tail_model.py [--config C2] [--slots 1024] [--k 0,1024,2048,3072,4096,all]
-                                 [--handover 6000:1500,24000:6000] [--out profiles/tail_levels_model.jsonl]
+    python scripts/tail_model.py [--config C2] [--slots 1024] [--k 0,1024,2048,3072,4096,all] [--group 1,2,3]
+                                 [--handover 50000:14000,20000:6000] [--out profiles/tail_groups_model.jsonl]
+
+(profiles/tail_levels_model.jsonl of §3.12: --group 1 --handover 6000:1500,24000:6000.)  The hand-over defaults are
+the measured ones: 50 k + 14 k cycles with the acquire-release fetch-adds under explicit fences that §3.12
+shipped, and the 20 k + 6 k estimated for the fence pair of §3.13 (the guide's figures for one release and one
+acquire; DESIGN.md §3.13 says what the counters gave).
 
 Per-level costs come from the C oracle: the bench batch solved with sqp_iters = 1 .. L on HPIPM's profile; the
 differences of the QP iteration counts are each solve's interior-point iterations per SQP-RTI iteration (level),
@@ -25,9 +30,19 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIN_CYCLES, IPM_CYCLES = 54.4e3, 80e3
 
 
-def simulate(levels, slots, K, load=0.0, save=0.0):
+def grouped(levels, group):
+    """the levels' costs summed by ticket group (csrc/mpcg_tail.h): level 0 alone, then `group` levels per
+    ticket, the last group possibly short.  group 1: the levels themselves"""
+    if group <= 1:
+        return levels
+    return [c[:1] + [sum(c[i:i + group]) for i in range(1, len(c), group)] for c in levels]
+
+
+def simulate(levels, slots, K, load=0.0, save=0.0, group=1):
     """levels: per solve the list of its levels' costs (batch order).  Returns (makespan, busy fraction,
-    hand-overs): busy = the levels' cycles / (slots x makespan), hand-overs = levels started from a carry block."""
+    hand-overs): busy = the levels' cycles / (slots x makespan), hand-overs = levels started from a carry block.
+    group > 1: a level ticket stands for that many levels after level 0 (the protocol is the same, on groups)."""
+    levels = grouped(levels, group)
     B = len(levels)
     K = min(max(K, 0), B)
     D = B - K
@@ -105,9 +120,10 @@ def main():
     ap.add_argument("--config", default="C2")
     ap.add_argument("--slots", type=int, default=1024)
     ap.add_argument("--k", default="0,1024,2048,3072,4096,all")
-    ap.add_argument("--handover", default="6000:1500,24000:6000", help="load:save cycles, comma separated")
+    ap.add_argument("--group", default="1,2,3", help="levels per ticket after level 0, comma separated")
+    ap.add_argument("--handover", default="50000:14000,20000:6000", help="load:save cycles, comma separated")
     ap.add_argument("--shuffles", type=int, default=3, help="also each case on this many shuffled batch orders")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "tail_levels_model.jsonl"))
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "tail_groups_model.jsonl"))
     a = ap.parse_args()
     levels, per, it = level_costs(a.config)
     B = len(levels)
@@ -124,18 +140,19 @@ def main():
     lines = [head]
     for ho in a.handover.split(","):
         load, save = (float(x) for x in ho.split(":"))
-        for ks in a.k.split(","):
-            K = B if ks == "all" else int(ks)
-            end, busy, n = simulate(levels, a.slots, K, load, save)
-            rec = {"config": a.config, "K": K, "load": load, "save": save, "makespan_vs_whole": round(end / base - 1, 4),
-                   "busy": round(busy, 4), "handovers": n}
-            sh = []
-            for seed in range(a.shuffles):
-                o = np.random.default_rng(seed).permutation(B)
-                lv = [levels[i] for i in o]
-                sh.append(round(simulate(lv, a.slots, K, load, save)[0] / simulate(lv, a.slots, 0)[0] - 1, 4))
-            rec["shuffled_orders_vs_whole"] = sh
-            lines.append(rec)
+        for G in (int(g) for g in a.group.split(",")):
+            for ks in a.k.split(","):
+                K = B if ks == "all" else int(ks)
+                end, busy, n = simulate(levels, a.slots, K, load, save, G)
+                rec = {"config": a.config, "K": K, "group": G, "load": load, "save": save,
+                       "makespan_vs_whole": round(end / base - 1, 4), "busy": round(busy, 4), "handovers": n}
+                sh = []
+                for seed in range(a.shuffles):
+                    o = np.random.default_rng(seed).permutation(B)
+                    lv = [levels[i] for i in o]
+                    sh.append(round(simulate(lv, a.slots, K, load, save, G)[0] / simulate(lv, a.slots, 0)[0] - 1, 4))
+                rec["shuffled_orders_vs_whole"] = sh
+                lines.append(rec)
     with open(a.out, "w") as f:
         for rec in lines:
             f.write(json.dumps(rec) + "\n")
