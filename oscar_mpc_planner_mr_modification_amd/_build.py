@@ -201,6 +201,29 @@ def build_tail_ab(name: str = "tail_off", force: bool = False) -> str:
                      sources=("mpcg_kernels.hip", "mpcg_prepare.hip", "mpcg_inst_tmpc20.hip"))
 
 
+# the linearisation that forms its iterate-independent work again at every SQP-RTI iteration:
+# `hrow_off` is the build tests/test_gpu_hrow_cache.py compares the production library with; the others switch
+# one piece on alone, or keep only M00, M01, M11 in the cache (A/B runs; build() does not make them).
+_HROW_OFF = {"cache": "-DMPCG_HROW_CACHE=0", "psi": "-DMPCG_PSI_SHARED=0"}
+HROW_AB = {"hrow_off": list(_HROW_OFF.values()),
+           **{f"hrow_only_{k}": [f for j, f in _HROW_OFF.items() if j != k] for k in _HROW_OFF},
+           "hrow_cache1": ["-DMPCG_HROW_CACHE=1"]}
+
+
+def build_hrow_ab(name: str = "hrow_off", force: bool = False) -> str:
+    """build/ab/<name>/libmpcg.so: libmpcg.so with HROW_AB[name]'s switches, instances of mpcg_inst_tmpc20.hip only"""
+    out = os.path.join(BUILD, "ab", name, "libmpcg.so")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    return build_lib(force=force, extra_flags=HROW_AB[name], out=out,
+                     sources=("mpcg_kernels.hip", "mpcg_prepare.hip", "mpcg_inst_tmpc20.hip"))
+
+
+def build_erk_psi_probe(force: bool = False) -> str:
+    """one wavefront around erk_unicycle of mpcg_device.h with and without sin / cos of psi given by the caller,
+    one (z, pi) per lane (tests/test_gpu_erk_psi_probe.py)"""
+    return _build_probe("erk_psi_probe", ["mpcg_device.h"], force)
+
+
 def build_cpp(config="C2", force: bool = False, verbose: bool = False) -> dict:
     """The drop-in C++ MPCPlanner::Solver for one generated solver
     (dimensions are compile-time, as in the reference): codegen into

@@ -292,9 +292,13 @@ __device__ __forceinline__ void erk_srow(const mpcg_problem& pr, double& sa, dou
     sv = pr.dt;
 }
 
-template <int NX>
+// PSI_GIVEN: sin / cos of psi come from the caller (Cfg::PSI_SHARED: the linearisation forms them once per lane,
+// for the h rows and for this map) instead of being formed here from the same argument: the same bits
+// (tests/test_gpu_erk_psi_probe.py).
+template <int NX, bool PSI_GIVEN = false>
 __device__ inline void erk_unicycle(const mpcg_problem& pr, const double z[NU + NX], const double* pi,
-                                    double xn[NX], double F[NX][NU + NX], double H[NU + NX][NU + NX]) {
+                                    double xn[NX], double F[NX][NU + NX], double H[NU + NX][NU + NX],
+                                    [[maybe_unused]] double spsi_in = 0.0, [[maybe_unused]] double cpsi_in = 0.0) {
     constexpr int NZ = NU + NX;
     const double a = z[0], w = z[1], psi = z[4], v = z[5];
     const int ns = pr.rk_steps;
@@ -311,7 +315,12 @@ __device__ inline void erk_unicycle(const mpcg_problem& pr, const double z[NU + 
         for (int j = 0; j < 4; ++j) hq[i][j] = 0.0;
     const double pix = pi ? pi[0] : 0.0, piy = pi ? pi[1] : 0.0;
     double cpsi, spsi;
-    sincos(psi, &spsi, &cpsi);
+    if constexpr (PSI_GIVEN) {
+        spsi = spsi_in;
+        cpsi = cpsi_in;
+    } else {
+        sincos(psi, &spsi, &cpsi);
+    }
     for (int st = 0; st < ns; ++st) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) {

@@ -267,6 +267,41 @@ struct Cfg {
 #endif
     static constexpr bool MIRROR_BLOCKS =
         MODEL_ == 0 && (MPCG_MIRROR_BLOCKS >= 2 || (MPCG_MIRROR_BLOCKS == 1 && PARTS == 3 && NX_ == 5));
+    // The linearisation's work that does not depend on the iterate, on the lean HPIPM-profile
+    // kernels of the three-part N <= 20 unicycle instances without LIN_PARAMS (C1, C2, the N 10 shape); the
+    // robust-profile and FULL kernels keep the linearisation they had.
+    // HROW_CACHE: an ellipsoid row's M00, M01, M11 (ell_metric: a square root, two reciprocals and a sincos of
+    // seven parameter words) are functions of the solve's parameter block alone.  The wave that starts a solve
+    // (or takes one over at a level ticket) forms them once, with h_rows' expressions, and stores them lane-major
+    // in its workgroup's slot of the global workspace ([slot][value][64 lanes]: hrow_idx); every linearisation
+    // loads the three doubles.  The same doubles into the same expressions: the same bits
+    // (tests/test_gpu_hrow_cache.py).  2 (the default: the faster one): the obstacle centres and
+    // the halfspace rows' coefficients are kept there too (every h slot, five values), so the h rows read no
+    // parameter word but the disc offset; 1: M00, M01, M11 of the slots with ellipsoid rows only.
+    // (MPCG_HROW_CACHE=0: formed at every linearisation, A/B and scripts/bitcmp.py)
+#ifndef MPCG_HROW_CACHE
+#define MPCG_HROW_CACHE 2
+#endif
+    // PSI_SHARED: one sincos(psi) per lane and linearisation, for the h rows and the ERK4 map (mpcg_device.h
+    // erk_unicycle PSI_GIVEN).  (MPCG_PSI_SHARED=0: formed in both, A/B and scripts/bitcmp.py)
+#ifndef MPCG_PSI_SHARED
+#define MPCG_PSI_SHARED 1
+#endif
+    // (up to 16 h rows: the road instance C2R, 18 rows, spills in its lean HPIPM kernel as it is -- 80 B/lane,
+    // 88 with these traits -- and keeps the linearisation it had)
+    static constexpr bool LIN_INVARIANTS = MODEL_ == 0 && PARTS == 3 && NX_ == 5 && !LIN_PARAMS && NH <= 16;
+    static constexpr int HROW_CACHE = (LIN_INVARIANTS && NE > 0) ? MPCG_HROW_CACHE : 0;
+    static constexpr bool PSI_SHARED = LIN_INVARIANTS && MPCG_PSI_SHARED > 0;
+    // the cached h slots of a lane: those that hold an ellipsoid row on some part (C2: 2..5 of 0..5), or all
+    static constexpr int HROW_R0 = HROW_CACHE >= 2 ? 0 : NL / PARTS;
+    static constexpr int HROW_SLOTS =
+        HROW_CACHE >= 2 ? HS : (HROW_CACHE == 1 ? (NL + NE - 1) / PARTS - NL / PARTS + 1 : 0);
+    static constexpr int HROW_VALS = HROW_CACHE >= 2 ? 5 : 3;
+    static constexpr int HROW_DOUBLES = HROW_CACHE > 0 ? HROW_SLOTS * HROW_VALS * 64 : 0;
+    // double `val` of cached slot `slot` (h slot HROW_R0 + slot) of lane `lane` in the cache region
+    __host__ __device__ static constexpr int hrow_idx(int slot, int val, int lane) {
+        return (slot * HROW_VALS + val) * 64 + lane;
+    }
     // the capsule's QP memory (mpcg_io.qp_in / qp_out, opaque): per slot and lane the row's
     // slack then multiplier ([2 s + {0, 1}][64 lanes]), then the QP step [N+1][NZ] and the
     // dynamics multipliers [N][NX]
@@ -368,10 +403,18 @@ template <class C>
 __host__ __device__ constexpr size_t itref_doubles() {
     return 2 * (size_t)(C::N + 1) * C::NZ + (size_t)C::N * C::NX;
 }
-// one workgroup's slot of the global workspace: the GFH blocks, then the refinement scratch
+// one workgroup's slot of the global workspace: the GFH blocks, then the refinement scratch, then the h rows'
+// cached constants (Cfg::HROW_CACHE, lane-major: Cfg::hrow_idx).  The region starts and ends on a multiple of 16
+// doubles, so that a value's 64 lanes are four whole 128-byte lines in every slot; without the region the slot is
+// what it was
+template <class C>
+__host__ __device__ constexpr size_t hrow_offset() {
+    const size_t o = gfh_doubles<C>() + itref_doubles<C>();
+    return C::HROW_DOUBLES > 0 ? (o + 15) / 16 * 16 : o;
+}
 template <class C>
 __host__ __device__ constexpr size_t slot_doubles() {
-    return gfh_doubles<C>() + itref_doubles<C>();
+    return hrow_offset<C>() + (size_t)C::HROW_DOUBLES;
 }
 // TAIL_LEVELS: the last solves of a work-queue launch run one SQP-RTI iteration per ticket (mpcg_tail.h,
 // DESIGN.md §3.12): the lean kernels of the queue instances with the split residual passes (C1, C2, the N 10
@@ -554,16 +597,77 @@ struct LaneRows : LaneBounds<C> {
     __device__ __forceinline__ bool h_on(int r) const { return k >= 1 && k < C::N && hrow(r) < C::NH; }
 };
 
+// The part of an obstacle-ellipsoid row that does not depend on the iterate: R' D R of the ellipsoid `o`
+// (seven parameter words: centre, angle, semi-axes, chi-square level, inflation) and the disc radius.  One
+// helper for h_rows and for hrow_fill (Cfg::HROW_CACHE), so that both round the same way.
+__device__ __forceinline__ void ell_metric(const double* o, double rdisc, double& M00, double& M01, double& M11) {
+    const double chi = sqrt(o[5]);
+    const double ra = o[3] * chi + rdisc + o[6];
+    const double rb = o[4] * chi + rdisc + o[6];
+    const double D0 = frcp(ra * ra), D1 = frcp(rb * rb);
+    double so, co;
+    sincos(o[2], &so, &co);
+    M00 = co * co * D0 + so * so * D1;
+    M01 = -co * so * D0 + so * co * D1;
+    M11 = so * so * D0 + co * co * D1;
+}
+
+// Cfg::HROW_CACHE: the constants of the h rows of the lane (stage k, part `part`), stored to the lane's column
+// `hc` of the workgroup's cache region -- an ellipsoid row's M00, M01, M11 (and, HROW_CACHE 2, its centre; a
+// halfspace row's three coefficients); zeros for the slots without such a row.  Called once in front of the
+// SQP loop: out of line, so that its registers are not the loop's.
+template <class C>
+__device__ __attribute__((noinline)) void hrow_fill(int i_ell0, int i_lin0, int i_disc_r, const double* pk, int k,
+                                                    int part, double* hc) {
+    static_assert(C::NS == 0, "ellipsoid and topology rows only");
+#pragma unroll
+    for (int s = 0; s < C::HROW_SLOTS; ++s) {
+        const int hh = part + C::PARTS * (C::HROW_R0 + s);
+        double v[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+        if (k >= 1 && k < C::N && hh < C::NH) {
+            if (hh >= C::NL) {
+                const double* o = pk + i_ell0 + 7 * (hh - C::NL);
+                ell_metric(o, pk[i_disc_r], v[0], v[1], v[2]);
+                v[3] = o[0];
+                v[4] = o[1];
+            } else if (C::HROW_CACHE >= 2) {
+                const double* c = pk + i_lin0 + 3 * hh;
+                v[0] = c[0];
+                v[1] = c[1];
+                v[2] = c[2];
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < C::HROW_VALS; ++i) hc[C::hrow_idx(s, i, 0)] = v[i];
+    }
+}
+
 // h values, signed gradients, bound gaps and the multiplier-weighted Hessian
 // (xx xy xp yy yp pp on x, y, psi) of the h rows of a lane at stage k.
-template <class C>
+// CACHE (Cfg::HROW_CACHE on the kernels that use it): the rows' constants come from the lane's column `hc` of
+// the cache region, all loads issued in front of the rows.  PSI_GIVEN: sin / cos of psi come from the caller
+template <class C, int CACHE = 0, bool PSI_GIVEN = false>
 __device__ __forceinline__ void h_rows(const mpcg_problem& pr, const double* __restrict__ pk, const double z[C::NZ],
                                        const LaneRows<C>& LR, const double* nlam, double hb6[6],
-                                       double (*Dg)[C::DGC], double* hd, double* disc) {
+                                       double (*Dg)[C::DGC], double* hd, double* disc,
+                                       [[maybe_unused]] const double* hc = nullptr,
+                                       [[maybe_unused]] double sp_in = 0.0, [[maybe_unused]] double cp_in = 0.0) {
     const double x = z[C::IX], y = z[C::IY], psi = z[C::IPSI];
-    const double rdisc = C::NE > 0 ? pk[pr.i_disc_r] : 0.0, off = pk[pr.i_disc_off];
+    [[maybe_unused]] double hcv[CACHE ? C::HROW_SLOTS : 1][5];
+    if constexpr (CACHE > 0) {
+#pragma unroll
+        for (int s = 0; s < C::HROW_SLOTS; ++s)
+#pragma unroll
+            for (int i = 0; i < C::HROW_VALS; ++i) hcv[s][i] = hc[C::hrow_idx(s, i, 0)];
+    }
+    const double rdisc = (C::NE > 0 && CACHE == 0) ? pk[pr.i_disc_r] : 0.0, off = pk[pr.i_disc_off];
     double sp, cp;
-    sincos(psi, &sp, &cp);
+    if constexpr (PSI_GIVEN) {
+        sp = sp_in;
+        cp = cp_in;
+    } else {
+        sincos(psi, &sp, &cp);
+    }
     const double dxp = -off * sp, dyp = off * cp, dxpp = -off * cp, dypp = -off * sp;
     if constexpr (C::LIN_PARAMS) {
         if (LR.part == 0) { disc[0] = off * cp; disc[1] = off * sp; disc[2] = dxp; disc[3] = dyp; }
@@ -576,6 +680,7 @@ __device__ __forceinline__ void h_rows(const mpcg_problem& pr, const double* __r
             // topology halfspace a1 x + a2 y - b <= 0 (guidance_constraints.py:355-370)
             if constexpr (!C::LIN_PARAMS) {  // else read from the parameters where used
                 const double* c = pk + pr.i_lin0 + 3 * hh;
+                if constexpr (CACHE >= 2) c = hcv[r < C::HROW_SLOTS ? r : 0];
                 hd[hh] = 0.0 - (c[0] * x + c[1] * y - c[2]);
                 Dg[hh][0] = c[0];
                 Dg[hh][1] = c[1];
@@ -597,15 +702,28 @@ __device__ __forceinline__ void h_rows(const mpcg_problem& pr, const double* __r
         } else {
             // obstacle ellipsoid d' R'DR d >= 1 (ellipsoid_constraints.py:435-489)
             const double* o = pk + pr.i_ell0 + 7 * (hh - C::NL);
-            const double chi = sqrt(o[5]);
-            const double ra = o[3] * chi + rdisc + o[6];
-            const double rb = o[4] * chi + rdisc + o[6];
-            const double D0 = frcp(ra * ra), D1 = frcp(rb * rb);
-            double so, co;
-            sincos(o[2], &so, &co);
-            const double M00 = co * co * D0 + so * so * D1;
-            const double M01 = -co * so * D0 + so * co * D1;
-            const double M11 = so * so * D0 + co * co * D1;
+            double M00, M01, M11;
+            if constexpr (CACHE > 0) {
+                // (the slots outside the cached range hold no ellipsoid row on any part)
+                constexpr int S1 = C::HROW_SLOTS - 1;
+                const double* cv = hcv[r < C::HROW_R0 ? 0 : (r - C::HROW_R0 > S1 ? S1 : r - C::HROW_R0)];
+                M00 = cv[0];
+                M01 = cv[1];
+                M11 = cv[2];
+                if constexpr (CACHE >= 2) o = cv + 3;
+            } else {
+                // (ell_metric's text: written out here, the kernels without the cache compile to the instructions
+                // they had)
+                const double chi = sqrt(o[5]);
+                const double ra = o[3] * chi + rdisc + o[6];
+                const double rb = o[4] * chi + rdisc + o[6];
+                const double D0 = frcp(ra * ra), D1 = frcp(rb * rb);
+                double so, co;
+                sincos(o[2], &so, &co);
+                M00 = co * co * D0 + so * so * D1;
+                M01 = -co * so * D0 + so * co * D1;
+                M11 = so * so * D0 + co * co * D1;
+            }
             const double ddx = x + off * cp - o[0], ddy = y + off * sp - o[1];
             const double Mdx = M00 * ddx + M01 * ddy, Mdy = M01 * ddx + M11 * ddy;
             const int he = C::LIN_PARAMS ? hh - C::NL : hh;

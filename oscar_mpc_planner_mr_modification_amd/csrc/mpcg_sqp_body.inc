@@ -298,6 +298,26 @@
     double res_eq = 0.0;
     double nlp_stat = 0.0, nlp_ineq = 0.0, nlp_comp = 0.0;  // NLP residuals of the last linearisation
     bool nlp_nonfinite = false;
+    // the linearisation's iterate-independent work (Cfg::HROW_CACHE, PSI_SHARED; DESIGN.md §3.14):
+    // the lean HPIPM-profile kernels, whose calls always come with a workspace (the refinement scratch)
+    constexpr bool LINV = !FULL && PROF == PROF_HPIPM;
+    constexpr int HCACHE = LINV ? C::HROW_CACHE : 0;
+    constexpr bool PSI_SHARED = LINV && C::PSI_SHARED;
+    // the lane's column of the workgroup's cache region, addressed again from the arguments at each use: kept
+    // in registers across the QP, the address costs the C2 kernel its scratch-free allocation (0 -> 48 B/lane)
+    [[maybe_unused]] auto hrow_column = [&]() -> double* {
+        int wg = (int)blockIdx.x;
+        asm volatile("" : "+s"(wg));
+        return gws + (size_t)wg * slot_doubles<C>() + hrow_offset<C>() + lane;
+    };
+    if constexpr (HCACHE > 0) {
+        // the first linearisation this wave runs for the solve: a whole-solve ticket, or a level ticket that is
+        // not continued in place (a continuation keeps the slot it filled: no other solve has run on the
+        // workgroup in between)
+        bool fill = true;
+        if constexpr (TAIL) fill = !tc.in_place;
+        if (fill) hrow_fill<C>(pr.i_ell0, pr.i_lin0, pr.i_disc_r, pk, k, part, hrow_column());
+    }
     int it0 = 0;
     if constexpr (TAIL) {
         if (resumed) {
@@ -347,7 +367,16 @@
 #pragma unroll
             for (int i = 0; i < NZ; ++i) zk[i] = S.z[ks][i];
             double hb6[6] = {0, 0, 0, 0, 0, 0};
-            if (k >= 1 && k < N) h_rows<C>(pr, pk, zk, LR, R.nlam, hb6, (double (*)[C::DGC])S.Dg[k], S.hd[k], S.disc[C::LIN_PARAMS ? k : 0]);
+            // PSI_SHARED: sin / cos of the lane's heading once, for its h rows and (part 0) its ERK4 map
+            [[maybe_unused]] double sps = 0.0, cps = 0.0;
+            if constexpr (PSI_SHARED) sincos(zk[C::IPSI], &sps, &cps);
+            if (k >= 1 && k < N) {
+                if constexpr (HCACHE > 0 || PSI_SHARED)
+                    h_rows<C, HCACHE, PSI_SHARED>(pr, pk, zk, LR, R.nlam, hb6, (double (*)[C::DGC])S.Dg[k], S.hd[k],
+                                                  S.disc[0], hrow_column(), sps, cps);
+                else
+                    h_rows<C>(pr, pk, zk, LR, R.nlam, hb6, (double (*)[C::DGC])S.Dg[k], S.hd[k], S.disc[C::LIN_PARAMS ? k : 0]);
+            }
             STAMP_LAP(10);
             // fold the h-row Hessian terms of parts 1.. into part 0 (fixed order)
             {
@@ -391,7 +420,8 @@
                     double F[NX][NZ];
                     stage_cost<NX>(pr, pk, zk, g, H, true);
                     STAMP_LAP(11);
-                    erk_unicycle<NX>(pr, zk, pi, xn, F, H);
+                    if constexpr (PSI_SHARED) erk_unicycle<NX, true>(pr, zk, pi, xn, F, H, sps, cps);
+                    else erk_unicycle<NX>(pr, zk, pi, xn, F, H);
                     STAMP_LAP(12);
 #pragma unroll
                     for (int i = 0; i < NX; ++i) {
