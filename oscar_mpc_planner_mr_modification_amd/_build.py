@@ -32,8 +32,15 @@ LAYERS = {
     "mpcg_active.h": {"sources": {"mpcg_active.hip": ["-ffp-contract=off"]}, "headers": ["mpcg_active.h"]},
     "mpcg_road.h": {"sources": {"mpcg_road.hip": ["-ffp-contract=off"]}, "headers": ["mpcg_road.h"]},
 }
-# csrc headers more than one layer includes: the entry points' checks and error text, the path evaluation
-LAYER_SHARED_HEADERS = ["mpcg_host.h", "mpcg_spline.h"]
+# the layers added after tests/test_layer_abi.py pinned the keys of LAYERS (decomp halfspaces): the same form,
+# taken in by lib_sources() and build_lib alike; tests/test_layer_abi_later.py holds them to the same comparison.
+# A change that may edit the pinned test folds the two tables together.
+LATER_LAYERS = {
+    "mpcg_decomp.h": {"sources": {"mpcg_decomp.hip": ["-ffp-contract=off"]}, "headers": ["mpcg_decomp.h"]},
+}
+# csrc headers more than one layer includes: the entry points' checks and error text, the path evaluation,
+# the wave arg-min
+LAYER_SHARED_HEADERS = ["mpcg_host.h", "mpcg_spline.h", "mpcg_wave.h"]
 HOST_SOURCES = ["host/mpcg_yaml.cpp", "host/mpcg_solver.cpp"]
 HOST_HEADERS = ["mpc_planner_solver/mpcg_yaml.h", "mpc_planner_solver/mpcg_config.h", "mpc_planner_solver/state.h",
                 "mpc_planner_solver/mpcg_solver_interface.h", "mpc_planner_solver/solver_interface.h"]
@@ -66,18 +73,23 @@ def _stale(target, deps):
 def lib_sources() -> dict:
     """every translation unit of libmpcg.so -> its extra flags: SOURCES, then the layers'"""
     srcs = dict(SOURCES)
-    for layer in LAYERS.values():
+    for layer in all_layers().values():
         srcs.update(layer["sources"])
     return srcs
+
+
+def all_layers() -> dict:
+    """LAYERS, then LATER_LAYERS"""
+    return {**LAYERS, **LATER_LAYERS}
 
 
 def build_lib(force: bool = False, verbose: bool = False, extra_flags=(), out: str = LIB, sources=None) -> str:
     """libmpcg.so (or a diagnostic / variant build of it with extra_flags at `out`; `sources`
     restricts the built-in instance files of such a build)"""
     srcs = {k: v for k, v in lib_sources().items() if sources is None or k not in SOURCES or k in sources}
-    layer_headers = LAYER_SHARED_HEADERS + [h for layer in LAYERS.values() for h in layer["headers"]]
+    layer_headers = LAYER_SHARED_HEADERS + [h for layer in all_layers().values() for h in layer["headers"]]
     deps = [os.path.join(CSRC, f) for f in list(lib_sources()) + HEADERS + layer_headers] + \
-        [os.path.join(INCLUDE, h) for h in ["mpcg.h"] + list(LAYERS)] + [__file__]
+        [os.path.join(INCLUDE, h) for h in ["mpcg.h"] + list(all_layers())] + [__file__]
     if not force and not _stale(out, deps):
         return out
     objdir = os.path.join(BUILD, "obj" + ("_" + "_".join(f.strip("-").replace("=", "") for f in extra_flags)

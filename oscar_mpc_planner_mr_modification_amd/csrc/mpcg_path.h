@@ -19,6 +19,7 @@
 
 #include "../../include/mpcg_path.h"  // the public header of the same name
 #include "mpcg_spline.h"              // PathLds, path_segment, path_point
+#include "mpcg_wave.h"                // wave_argmin
 
 namespace mpcg {
 
@@ -39,19 +40,9 @@ __device__ __forceinline__ double path_dist2(double px, double py, double qx, do
     return d == d ? d : __longlong_as_double(0x7ff0000000000000LL);
 }
 
-// the lane of the smallest (d, lane) of the wavefront, the same value in every lane
-__device__ __forceinline__ int path_argmin(double d, int lane) {
-    int l = lane;
-    for (int off = PATH_LANES / 2; off > 0; off >>= 1) {
-        const double od = __shfl_xor(d, off, PATH_LANES);
-        const int ol = __shfl_xor(l, off, PATH_LANES);
-        if (od < d || (od == d && ol < l)) {
-            d = od;
-            l = ol;
-        }
-    }
-    return __builtin_amdgcn_readfirstlane(l);
-}
+// the lane of the smallest (d, lane) of the wavefront, the same value in every lane (mpcg_wave.h)
+static_assert(PATH_LANES == WAVE_LANES, "one sample per lane of the wavefront");
+__device__ __forceinline__ int path_argmin(double d, int lane) { return wave_argmin(d, lane); }
 
 __global__ __launch_bounds__(64) void path_update_kernel(int n_scenes, int nx, int npar, int i_spline0, int n_seg,
                                                          mpcg_path_table tb, const double* __restrict__ state,

@@ -1,7 +1,8 @@
 // mpcg_spline.h — one path of the table of include/mpcg_path.h staged in LDS and its piecewise
-// cubic evaluation, shared by the reference-path tracking (mpcg_path.h) and the road-boundary
-// halfspaces (mpcg_road.h).  Explicitly rounded operations in the host restatements' order
-// (paths.py, roads.py): compiled without contraction, the values agree bit for bit.
+// cubic evaluation, shared by the reference-path tracking (mpcg_path.h), the road-boundary
+// halfspaces (mpcg_road.h) and the decomp halfspaces (mpcg_decomp.h).  Explicitly rounded operations
+// in the host restatements' order (paths.py, roads.py, decomp.py): compiled without contraction, the
+// values agree bit for bit.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -15,8 +15,8 @@ import numpy as np
 # from torch tensors are valid in our kernels.
 import torch
 
-from .native_spec import (ABI_VERSION, ACTIVE_EXPORTS, DEFAULT_OPTIONS, EXPORTS, FLEET_EXPORTS,  # noqa: F401
-                          GUIDANCE_CANDIDATES,
+from .native_spec import (ABI_VERSION, ACTIVE_EXPORTS, DECOMP_EXPORTS, DEFAULT_OPTIONS, EXPORTS,  # noqa: F401
+                          FLEET_EXPORTS, GUIDANCE_CANDIDATES, LATER_SIGNATURES, MpcgDecompIo, MpcgDecompSettings,
                           GUIDANCE_EXPORTS, INFO_STRIDE, NU, NVAR, NX, PATH_EXPORTS, SIGNATURES, STATS_STRIDE, UNICYCLE_LB,
                           UNICYCLE_UB, MpcgFleetSettings, MpcgFleetState, MpcgGuidanceOut, MpcgGuidanceSettings,
                           MpcgGuidanceState, MpcgIo, MpcgPathSettings, MpcgPathTable, MpcgProblem, MpcgRoadIo,
@@ -33,7 +33,7 @@ def _load():
         raise ImportError(f"{LIB_PATH} not built: run `python -c 'import __graft_entry__ as g; g.build()'` "
                           "(hipcc --offload-arch=gfx950); there is no CPU fallback")
     lib = C.CDLL(LIB_PATH)
-    for group in SIGNATURES.values():
+    for group in list(SIGNATURES.values()) + list(LATER_SIGNATURES.values()):
         for name, (restype, argtypes) in group.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes
@@ -522,6 +522,48 @@ def road_halfspaces_device(pr: MpcgProblem, G: int, max_obstacles: int, settings
                                   dtable["path_of_host"].ctypes.data, C.byref(io), _ptr(params), _ptr(halfspaces),
                                   _stream(stream, params.device))
     _check(rc, "mpcg_road_halfspaces")
+
+
+def decomp_points_device(occ, n_occ, device) -> dict:
+    """The occupied points occ (S, P, 2) and their counts n_occ (S,) (decomp.make_c3_decomp_scenes) as device
+    tensors, with the host copy of the counts the entry point checks (dict occ, n_occ, n_occ_host)."""
+    occ = np.array(occ, np.float64, order="C")
+    assert occ.ndim == 3 and occ.shape[2] == 2, occ.shape
+    host = np.array(n_occ, np.int32, order="C")
+    assert host.shape == (occ.shape[0],)
+    return dict(occ=torch.from_numpy(occ).to(device), n_occ=torch.from_numpy(host).to(device), n_occ_host=host)
+
+
+def decomp_halfspaces_device(pr: MpcgProblem, G: int, settings: MpcgDecompSettings, dtable: dict, points: dict, params,
+                             state, main_warm=None, halfspaces=None, n_found=None, minor_axis=None, stream=None):
+    """mpcg_decomp_halfspaces (include/mpcg_decomp.h): the max_constraints = pr.n_scen decomp rows of all N
+    stages into params (S*G, N, npar), every planner of a scene alike, from the occupied points `points`
+    (decomp_points_device) around the path points at s advanced by the `v` entries of main_warm
+    (S, N+1, nu+nx), or of the braking plan from state (S, nx) when it is None.  `dtable`: path_table_device;
+    halfspaces (S, N, max_constraints, 3), n_found (S, N) int32 and minor_axis (S, N) are optional outputs.
+    Asynchronous on `stream`; nothing is allocated."""
+    S, N = dtable["path_of"].numel(), pr.N
+    occ, n_occ = points["occ"], points["n_occ"]
+    P = occ.shape[1]
+    _dev("params", params, F64, (S * G, N, pr.npar))
+    _dev("state", state, F64, (S, pr.nx))
+    _dev("occ", occ, F64, (S, P, 2))
+    _dev("n_occ", n_occ, I32, S)
+    assert points["n_occ_host"].shape == (S,) and points["n_occ_host"].dtype == np.int32
+    if main_warm is not None:
+        _dev("main_warm", main_warm, F64, (S, N + 1, pr.nu + pr.nx))
+    if halfspaces is not None:
+        _dev("halfspaces", halfspaces, F64, (S, N, pr.n_scen, 3))
+    if n_found is not None:
+        _dev("n_found", n_found, I32, (S, N))
+    if minor_axis is not None:
+        _dev("minor_axis", minor_axis, F64, (S, N))
+    io = MpcgDecompIo(_addr(state), _addr(main_warm), occ.data_ptr() if P else None, _addr(n_occ), int(P))
+    rc = lib.mpcg_decomp_halfspaces(C.byref(pr), S, G, C.byref(settings), C.byref(dtable["native"]),
+                                    dtable["path_of_host"].ctypes.data, C.byref(io), points["n_occ_host"].ctypes.data,
+                                    _ptr(params), _ptr(halfspaces), _ptr(n_found), _ptr(minor_axis),
+                                    _stream(stream, params.device))
+    _check(rc, "mpcg_decomp_halfspaces")
 
 
 def _guidance_state(gstate: dict, S: int, G: int, N: int) -> MpcgGuidanceState:

@@ -207,6 +207,21 @@ class MpcgRoadIo(C.Structure):
 ROAD_CENTERLINE, ROAD_BOUNDS, ROAD_MAX_N = 0, 1, 32
 
 
+class MpcgDecompSettings(C.Structure):
+    """Mirror of `mpcg_decomp_settings` (include/mpcg_decomp.h)."""
+    _fields_ = [("range", C.c_double), ("deceleration", C.c_double)]
+
+
+class MpcgDecompIo(C.Structure):
+    """Mirror of `mpcg_decomp_io` (include/mpcg_decomp.h)."""
+    _fields_ = [("state", C.c_void_p), ("main_warm", C.c_void_p), ("occ", C.c_void_p), ("n_occ", C.c_void_p),
+                ("max_points", C.c_int)]
+
+
+# the decomp halfspaces (include/mpcg_decomp.h)
+DECOMP_MAX_POINTS, DECOMP_MAX_N, DECOMP_MAX_ROWS, DECOMP_EPS = 1024, 32, 64, 1e-10
+
+
 class MpcgGuidanceSettings(C.Structure):
     """Mirror of `mpcg_guidance_settings` (include/mpcg_guidance.h)."""
     _fields_ = [("robot_radius", C.c_double), ("v_ref", C.c_double), ("consistency_on_non_guided", C.c_int)]
@@ -317,3 +332,19 @@ PATH_EXPORTS = tuple(SIGNATURES["mpcg_path.h"])
 ROAD_EXPORTS = tuple(SIGNATURES["mpcg_road.h"])
 GUIDANCE_EXPORTS = tuple(SIGNATURES["mpcg_guidance.h"])
 ACTIVE_EXPORTS = tuple(SIGNATURES["mpcg_active.h"])
+
+
+def _later_signatures() -> dict:
+    i, vp, ptr = C.c_int, C.c_void_p, C.POINTER
+    return {
+        "mpcg_decomp.h": {
+            "mpcg_decomp_halfspaces": (i, [ptr(MpcgProblem), i, i, ptr(MpcgDecompSettings), ptr(MpcgPathTable), vp,
+                                           ptr(MpcgDecompIo), vp, vp, vp, vp, vp, vp]),
+        },
+    }
+
+
+# The layers of _build.LATER_LAYERS, in the form of SIGNATURES (whose key set tests/test_layer_abi.py pins to the
+# first five layers); native._load() applies both tables in one loop.
+LATER_SIGNATURES = _later_signatures()
+DECOMP_EXPORTS = tuple(LATER_SIGNATURES["mpcg_decomp.h"])
