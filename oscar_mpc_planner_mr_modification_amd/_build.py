@@ -38,6 +38,12 @@ LAYERS = {
 LATER_LAYERS = {
     "mpcg_decomp.h": {"sources": {"mpcg_decomp.hip": ["-ffp-contract=off"]}, "headers": ["mpcg_decomp.h"]},
 }
+# the layers added after tests/test_layer_abi_later.py pinned the keys of LATER_LAYERS in turn (the SH-MPC scenario
+# sampler): the same form once more.  tests/test_layer_abi_open.py checks every entry it finds here and pins no key
+# set, so the next layer is one more row of this table; all_layers() stays the two pinned tables.
+OPEN_LAYERS = {
+    "mpcg_scenario.h": {"sources": {"mpcg_scenario.hip": ["-ffp-contract=off"]}, "headers": ["mpcg_scenario.h"]},
+}
 # csrc headers more than one layer includes: the entry points' checks and error text, the path evaluation,
 # the wave arg-min
 LAYER_SHARED_HEADERS = ["mpcg_host.h", "mpcg_spline.h", "mpcg_wave.h"]
@@ -73,7 +79,7 @@ def _stale(target, deps):
 def lib_sources() -> dict:
     """every translation unit of libmpcg.so -> its extra flags: SOURCES, then the layers'"""
     srcs = dict(SOURCES)
-    for layer in all_layers().values():
+    for layer in linked_layers().values():
         srcs.update(layer["sources"])
     return srcs
 
@@ -83,13 +89,18 @@ def all_layers() -> dict:
     return {**LAYERS, **LATER_LAYERS}
 
 
+def linked_layers() -> dict:
+    """every layer linked into libmpcg.so: all_layers(), then OPEN_LAYERS"""
+    return {**all_layers(), **OPEN_LAYERS}
+
+
 def build_lib(force: bool = False, verbose: bool = False, extra_flags=(), out: str = LIB, sources=None) -> str:
     """libmpcg.so (or a diagnostic / variant build of it with extra_flags at `out`; `sources`
     restricts the built-in instance files of such a build)"""
     srcs = {k: v for k, v in lib_sources().items() if sources is None or k not in SOURCES or k in sources}
-    layer_headers = LAYER_SHARED_HEADERS + [h for layer in all_layers().values() for h in layer["headers"]]
+    layer_headers = LAYER_SHARED_HEADERS + [h for layer in linked_layers().values() for h in layer["headers"]]
     deps = [os.path.join(CSRC, f) for f in list(lib_sources()) + HEADERS + layer_headers] + \
-        [os.path.join(INCLUDE, h) for h in ["mpcg.h"] + list(all_layers())] + [__file__]
+        [os.path.join(INCLUDE, h) for h in ["mpcg.h"] + list(linked_layers())] + [__file__]
     if not force and not _stale(out, deps):
         return out
     objdir = os.path.join(BUILD, "obj" + ("_" + "_".join(f.strip("-").replace("=", "") for f in extra_flags)

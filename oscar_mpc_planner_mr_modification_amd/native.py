@@ -20,7 +20,8 @@ from .native_spec import (ABI_VERSION, ACTIVE_EXPORTS, DECOMP_EXPORTS, DEFAULT_O
                           GUIDANCE_EXPORTS, INFO_STRIDE, NU, NVAR, NX, PATH_EXPORTS, SIGNATURES, STATS_STRIDE, UNICYCLE_LB,
                           UNICYCLE_UB, MpcgFleetSettings, MpcgFleetState, MpcgGuidanceOut, MpcgGuidanceSettings,
                           MpcgGuidanceState, MpcgIo, MpcgPathSettings, MpcgPathTable, MpcgProblem, MpcgRoadIo,
-                          MpcgRoadSettings, MpcgSceneIo, MpcgStepIo, MpcgScenarioIo, ROAD_EXPORTS, problem_from_layout)
+                          MpcgRoadSettings, MpcgSceneIo, MpcgStepIo, MpcgScenarioIo, ROAD_EXPORTS, problem_from_layout,
+                          OPEN_SIGNATURES, SCENARIO_EXPORTS, MpcgScenarioSampleIo, MpcgScenarioStepIo)
 
 PKG = os.path.dirname(os.path.abspath(__file__))
 # MPCG_LIB selects a diagnostic build (e.g. libmpcg_stamps.so); default the production library
@@ -33,7 +34,7 @@ def _load():
         raise ImportError(f"{LIB_PATH} not built: run `python -c 'import __graft_entry__ as g; g.build()'` "
                           "(hipcc --offload-arch=gfx950); there is no CPU fallback")
     lib = C.CDLL(LIB_PATH)
-    for group in list(SIGNATURES.values()) + list(LATER_SIGNATURES.values()):
+    for group in list(SIGNATURES.values()) + list(LATER_SIGNATURES.values()) + list(OPEN_SIGNATURES.values()):
         for name, (restype, argtypes) in group.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes
@@ -564,6 +565,94 @@ def decomp_halfspaces_device(pr: MpcgProblem, G: int, settings: MpcgDecompSettin
                                     _ptr(params), _ptr(halfspaces), _ptr(n_found), _ptr(minor_axis),
                                     _stream(stream, params.device))
     _check(rc, "mpcg_decomp_halfspaces")
+
+
+def _scenario_sample_io(pr: MpcgProblem, P: int, obst, obst_meta, bank, robot_radius, deceleration, stage_params=None,
+                        state=None, main_warm=None, batch_idx=None, seed: int = 0, draw: int = 0):
+    """The mpcg_scenario_sample_io of S scenes x P copies, every tensor checked: (io, S, n_obs, n_per)."""
+    S, n_obs = obst.shape[0], obst.shape[1]
+    n_batches, n_per = bank.shape[0], bank.shape[1]
+    _dev("obst", obst, F64, (S, n_obs, pr.N, 5))
+    _dev("obst_meta", obst_meta, F64, (S, n_obs, 2))
+    _dev("bank", bank, F64, (n_batches, n_per, 2))
+    if stage_params is not None:
+        _dev("stage_params", stage_params, F64, (S, pr.npar))
+    if state is not None:
+        _dev("state", state, F64, (S, pr.nx))
+    if main_warm is not None:
+        _dev("main_warm", main_warm, F64, (S, pr.N + 1, pr.nu + pr.nx))
+    if batch_idx is not None:
+        _dev("batch_idx", batch_idx, I32, (S * P, n_obs))
+    mask = (1 << 64) - 1
+    io = MpcgScenarioSampleIo(_addr(stage_params), _addr(state), _addr(main_warm), obst.data_ptr(), obst_meta.data_ptr(),
+                              bank.data_ptr(), _addr(batch_idx), int(n_obs), int(n_per), int(n_batches),
+                              int(seed) & mask, int(draw) & mask, float(robot_radius), float(deceleration))
+    return io, S, n_obs, n_per
+
+
+def scenario_sample_prepare_device(pr: MpcgProblem, n_solvers: int, stage_params, state, obst, obst_meta, bank,
+                                   robot_radius: float, deceleration: float, main_warm=None, batch_idx=None,
+                                   seed: int = 0, draw: int = 0, out=None, stream=None):
+    """mpcg_scenario_sample_prepare (include/mpcg_scenario.h): the SH-MPC solver inputs of S scenes x P copies
+    from the predictions obst (S, n_obs, N, 5) / obst_meta (S, n_obs, 2) and the bank (n_batches, n_per, 2) of
+    standard-normal pairs, sampled and reduced in one launch.  The batch of copy sol for obstacle j is
+    batch_idx (S*P, n_obs) int32 when given, else derived from (seed, draw).  Returns dict(params, warm,
+    xinit) of device tensors (`out` when given: nothing is allocated); asynchronous on `stream`."""
+    io, S, _, _ = _scenario_sample_io(pr, n_solvers, obst, obst_meta, bank, robot_radius, deceleration, stage_params,
+                                      state, main_warm, batch_idx, seed, draw)
+    assert stage_params is not None and state is not None
+    B, N, nx, dev = S * n_solvers, pr.N, pr.nx, obst.device
+    if out is None:
+        out = dict(params=torch.empty((B, N, pr.npar), dtype=F64, device=dev),
+                   warm=torch.empty((B, N + 1, pr.nu + nx), dtype=F64, device=dev),
+                   xinit=torch.empty((B, nx), dtype=F64, device=dev))
+    else:
+        _dev("params", out["params"], F64, (B, N, pr.npar))
+        _dev("warm", out["warm"], F64, (B, N + 1, pr.nu + nx))
+        _dev("xinit", out["xinit"], F64, (B, nx))
+    rc = lib.mpcg_scenario_sample_prepare(C.byref(pr), S, n_solvers, C.byref(io), _ptr(out["params"]),
+                                          _ptr(out["warm"]), _ptr(out["xinit"]), _stream(stream, dev))
+    _check(rc, "mpcg_scenario_sample_prepare")
+    return out
+
+
+def scenario_samples_device(pr: MpcgProblem, n_solvers: int, obst, obst_meta, bank, batch_idx=None, seed: int = 0,
+                            draw: int = 0, out=None, stream=None):
+    """mpcg_scenario_samples (include/mpcg_scenario.h): the sample tensor (S*P, N, M, 2) of mpcg_scenario_io
+    (stage 0: the stage-1 values) the fused launch never stores; for tests, recordings and visualisation."""
+    io, S, n_obs, n_per = _scenario_sample_io(pr, n_solvers, obst, obst_meta, bank, 0.0, 0.0, batch_idx=batch_idx,
+                                              seed=seed, draw=draw)
+    shape = (S * n_solvers, pr.N, n_obs * n_per, 2)
+    if out is None:
+        out = torch.empty(shape, dtype=F64, device=obst.device)
+    _dev("samples", out, F64, shape)
+    rc = lib.mpcg_scenario_samples(C.byref(pr), S, n_solvers, C.byref(io), _ptr(out), _stream(stream, obst.device))
+    _check(rc, "mpcg_scenario_samples")
+    return out
+
+
+def scenario_advance_device(pr: MpcgProblem, S: int, n_solvers: int, best, exit_code, xtraj, utraj, lam_out, state_next,
+                            deceleration: float, main_warm, lam_next=None, stream=None):
+    """mpcg_scenario_advance (include/mpcg_scenario.h): main_warm (S, N+1, nu+nx) of the next SH-MPC step -- the
+    winner's output shifted forward, or the braking plan from state_next (S, nx) where best (S,) int32 is
+    -1 -- and lam_next (S*P, N, nx+nh), each copy's lam_out when its exit code is 1, zero otherwise.
+    Asynchronous on `stream`; nothing is allocated."""
+    B, N, nx = S * n_solvers, pr.N, pr.nx
+    _dev("best", best, I32, S)
+    _dev("exit_code", exit_code, I32, B)
+    _dev("xtraj", xtraj, F64, (B, N + 1, nx))
+    _dev("utraj", utraj, F64, (B, N, pr.nu))
+    _dev("state_next", state_next, F64, (S, nx))
+    _dev("main_warm", main_warm, F64, (S, N + 1, pr.nu + nx))
+    if lam_out is not None:
+        _dev("lam_out", lam_out, F64, (B, N, lam_stride(pr)))
+    if lam_next is not None:
+        _dev("lam_next", lam_next, F64, (B, N, lam_stride(pr)))
+    io = MpcgScenarioStepIo(best.data_ptr(), exit_code.data_ptr(), xtraj.data_ptr(), utraj.data_ptr(), _addr(lam_out),
+                            state_next.data_ptr(), float(deceleration))
+    rc = lib.mpcg_scenario_advance(C.byref(pr), S, n_solvers, C.byref(io), _ptr(main_warm), _ptr(lam_next),
+                                   _stream(stream, xtraj.device))
+    _check(rc, "mpcg_scenario_advance")
 
 
 def _guidance_state(gstate: dict, S: int, G: int, N: int) -> MpcgGuidanceState:

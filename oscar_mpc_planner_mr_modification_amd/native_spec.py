@@ -348,3 +348,42 @@ def _later_signatures() -> dict:
 # first five layers); native._load() applies both tables in one loop.
 LATER_SIGNATURES = _later_signatures()
 DECOMP_EXPORTS = tuple(LATER_SIGNATURES["mpcg_decomp.h"])
+
+
+class MpcgScenarioSampleIo(C.Structure):
+    """Mirror of `mpcg_scenario_sample_io` (include/mpcg_scenario.h)."""
+    _fields_ = [("stage_params", C.c_void_p), ("state", C.c_void_p), ("main_warm", C.c_void_p),
+                ("obst", C.c_void_p), ("obst_meta", C.c_void_p), ("bank", C.c_void_p), ("batch_idx", C.c_void_p),
+                ("n_obs", C.c_int), ("n_per", C.c_int), ("n_batches", C.c_int),
+                ("seed", C.c_ulonglong), ("draw", C.c_ulonglong),
+                ("robot_radius", C.c_double), ("deceleration", C.c_double)]
+
+
+class MpcgScenarioStepIo(C.Structure):
+    """Mirror of `mpcg_scenario_step_io` (include/mpcg_scenario.h)."""
+    _fields_ = [("best", C.c_void_p), ("exit_code", C.c_void_p), ("xtraj", C.c_void_p), ("utraj", C.c_void_p),
+                ("lam_out", C.c_void_p), ("state_next", C.c_void_p), ("deceleration", C.c_double)]
+
+
+# the scenario sampler (include/mpcg_scenario.h)
+SCENARIO_MAX_SAMPLES, SCENARIO_MAX_OBS, SCENARIO_MAX_N, SCENARIO_MAX_ROWS = 2048, 64, 32, 32
+SCENARIO_MIX_C1, SCENARIO_MIX_C2 = 0x9E3779B97F4A7C15, 0xD1B54A32D192ED03
+SCENARIO_MIX_M1, SCENARIO_MIX_M2 = 0xBF58476D1CE4E5B9, 0x94D049BB133111EB
+
+
+def _open_signatures() -> dict:
+    i, vp, ptr = C.c_int, C.c_void_p, C.POINTER
+    P, SIO = ptr(MpcgProblem), ptr(MpcgScenarioSampleIo)
+    return {
+        "mpcg_scenario.h": {
+            "mpcg_scenario_sample_prepare": (i, [P, i, i, SIO, vp, vp, vp, vp]),
+            "mpcg_scenario_samples": (i, [P, i, i, SIO, vp, vp]),
+            "mpcg_scenario_advance": (i, [P, i, i, ptr(MpcgScenarioStepIo), vp, vp, vp]),
+        },
+    }
+
+
+# The layers of _build.OPEN_LAYERS, in the form of SIGNATURES: the table a new layer adds its group to
+# (tests/test_layer_abi_open.py pins no key set); native._load() applies all three tables in one loop.
+OPEN_SIGNATURES = _open_signatures()
+SCENARIO_EXPORTS = tuple(OPEN_SIGNATURES["mpcg_scenario.h"])

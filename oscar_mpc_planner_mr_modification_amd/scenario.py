@@ -149,46 +149,67 @@ def previous_plan(layout: Layout, x0: np.ndarray, path, obstacles, rng) -> np.nd
     return warm
 
 
+def shmpc_scene_world(layout: Layout, n_obs: int, scene_seed: int) -> dict:
+    """The seeded world of one SH-MPC scene, the draws make_shmpc_scenes and
+    scenario_sampler.make_shmpc_prediction_scenes share: dict(stage_params (npar,), state (nx,),
+    means (n_obs, N, 2) the obstacles' constant-velocity mean paths at t = k dt, velocity (n_obs, 2),
+    path (coef, starts, s_ego))."""
+    N, dt, ix = layout.N, layout.dt, layout.idx
+    tk = dt * np.arange(N)
+    rng = np.random.default_rng(scene_seed)
+    coef, starts = _path(rng, layout.n_seg)
+    s_ego = rng.uniform(0.0, 1.0)
+    p_on, t_on = _path_eval(coef, starts, s_ego)
+    n_on = np.array([-t_on[1], t_on[0]])
+    ego_pos = p_on + rng.normal(0, 0.2) * n_on
+    v0 = rng.uniform(0.0, 2.0)
+    psi0 = np.arctan2(t_on[1], t_on[0]) + rng.normal(0.0, 0.1)
+    state = np.zeros(layout.nx)
+    state[:5] = (ego_pos[0], ego_pos[1], psi0, v0, s_ego)
+    means = np.zeros((n_obs, N, 2))
+    velocity = np.zeros((n_obs, 2))
+    for j in range(n_obs):
+        ahead = rng.uniform(2.0, SPAWN_AHEAD)
+        lat = rng.uniform(-SPAWN_LAT, SPAWN_LAT)
+        pj, tj = _path_eval(coef, starts, s_ego + ahead)
+        nj = np.array([-tj[1], tj[0]])
+        vj = rng.normal(0.0, 0.7, size=2)
+        velocity[j] = vj
+        means[j] = (pj + lat * nj)[None, :] + vj[None, :] * tk[:, None]
+    base = np.zeros(layout.npar)
+    for name in ("acceleration", "angular_velocity", "velocity", "reference_velocity", "contour", "lag",
+                 "terminal_angle", "terminal_contouring"):
+        base[ix(name)] = SETTINGS_WEIGHTS[name]
+    base[ix("slack")] = SLACK_WEIGHT
+    for j in range(layout.n_seg):
+        for ax, axn in enumerate("xy"):
+            for ci, cn in enumerate("abcd"):
+                base[ix(f"spline_{axn}{j}_{cn}")] = coef[j, ax, ci]
+        base[ix(f"spline{j}_start")] = starts[j]
+    base[ix("ego_disc_0_offset")] = 0.0
+    return dict(stage_params=base, state=state, means=means, velocity=velocity, path=(coef, starts, s_ego))
+
+
+def shmpc_previous_plan(layout: Layout, world: dict, scene_seed: int) -> np.ndarray:
+    """previous_plan around the mean paths of `world` (shmpc_scene_world), patterns from stream 0 of the scene's seed"""
+    means, dt = world["means"], layout.dt
+    obstacles = [(means[j, 0], (means[j, 1] - means[j, 0]) / dt) for j in range(len(means))]
+    return previous_plan(layout, world["state"], world["path"], obstacles, np.random.default_rng([scene_seed, 0]))
+
+
 def make_shmpc_scenes(layout: Layout, n_scenes: int, n_solvers: int = PARALLEL_SOLVERS, n_obs: int = 12,
                       n_samples: int = 100, seed: int = SEED0, first_scene: int = 0,
                       previous_plan_warm: bool = True) -> ScenarioScenes:
     assert layout.model == "unicycle_slack" and layout.n_scen > 0
-    N, dt, npar, ix = layout.N, layout.dt, layout.npar, layout.idx
+    N, dt, npar = layout.N, layout.dt, layout.npar
     S, P, M = n_scenes, n_solvers, n_obs * n_samples
     stage_params = np.zeros((S, npar))
     state = np.zeros((S, layout.nx))
     samples = np.zeros((S * P, N, M, 2))
     main_warm = np.zeros((S, N + 1, layout.nvar)) if previous_plan_warm else None
-    tk = dt * np.arange(N)
     for sc in range(S):
-        rng = np.random.default_rng(seed + first_scene + sc)
-        coef, starts = _path(rng, layout.n_seg)
-        s_ego = rng.uniform(0.0, 1.0)
-        p_on, t_on = _path_eval(coef, starts, s_ego)
-        n_on = np.array([-t_on[1], t_on[0]])
-        ego_pos = p_on + rng.normal(0, 0.2) * n_on
-        v0 = rng.uniform(0.0, 2.0)
-        psi0 = np.arctan2(t_on[1], t_on[0]) + rng.normal(0.0, 0.1)
-        state[sc, :5] = (ego_pos[0], ego_pos[1], psi0, v0, s_ego)
-        means = np.zeros((n_obs, N, 2))
-        for j in range(n_obs):
-            ahead = rng.uniform(2.0, SPAWN_AHEAD)
-            lat = rng.uniform(-SPAWN_LAT, SPAWN_LAT)
-            pj, tj = _path_eval(coef, starts, s_ego + ahead)
-            nj = np.array([-tj[1], tj[0]])
-            vj = rng.normal(0.0, 0.7, size=2)
-            means[j] = (pj + lat * nj)[None, :] + vj[None, :] * tk[:, None]
-        base = stage_params[sc]
-        for name in ("acceleration", "angular_velocity", "velocity", "reference_velocity", "contour", "lag",
-                     "terminal_angle", "terminal_contouring"):
-            base[ix(name)] = SETTINGS_WEIGHTS[name]
-        base[ix("slack")] = SLACK_WEIGHT
-        for j in range(layout.n_seg):
-            for ax, axn in enumerate("xy"):
-                for ci, cn in enumerate("abcd"):
-                    base[ix(f"spline_{axn}{j}_{cn}")] = coef[j, ax, ci]
-            base[ix(f"spline{j}_start")] = starts[j]
-        base[ix("ego_disc_0_offset")] = 0.0
+        world = shmpc_scene_world(layout, n_obs, seed + first_scene + sc)
+        state[sc], stage_params[sc], means = world["state"], world["stage_params"], world["means"]
         for s in range(P):
             srng = np.random.default_rng([seed + first_scene + sc, s + 1])
             # (n_obs, n_samples, N, 2): integrated velocity noise, zero at stage 0
@@ -198,9 +219,7 @@ def make_shmpc_scenes(layout: Layout, n_scenes: int, n_solvers: int = PARALLEL_S
             smp = means[:, None] + walk                      # (n_obs, n_samples, N, 2)
             samples[sc * P + s] = smp.transpose(2, 0, 1, 3).reshape(N, M, 2)
         if main_warm is not None:
-            obstacles = [(means[j, 0], (means[j, 1] - means[j, 0]) / dt) for j in range(n_obs)]
-            main_warm[sc] = previous_plan(layout, state[sc], (coef, starts, s_ego), obstacles,
-                                          np.random.default_rng([seed + first_scene + sc, 0]))
+            main_warm[sc] = shmpc_previous_plan(layout, world, seed + first_scene + sc)
     return ScenarioScenes(stage_params=stage_params, state=state, samples=samples, n_solvers=P, main_warm=main_warm)
 
 
