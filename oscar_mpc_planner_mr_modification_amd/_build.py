@@ -39,10 +39,11 @@ LATER_LAYERS = {
     "mpcg_decomp.h": {"sources": {"mpcg_decomp.hip": ["-ffp-contract=off"]}, "headers": ["mpcg_decomp.h"]},
 }
 # the layers added after tests/test_layer_abi_later.py pinned the keys of LATER_LAYERS in turn (the SH-MPC scenario
-# sampler): the same form once more.  tests/test_layer_abi_open.py checks every entry it finds here and pins no key
+# sampler, then the tracked-object layer): the same form once more.  tests/test_layer_abi_open.py checks every entry it finds here and pins no key
 # set, so the next layer is one more row of this table; all_layers() stays the two pinned tables.
 OPEN_LAYERS = {
     "mpcg_scenario.h": {"sources": {"mpcg_scenario.hip": ["-ffp-contract=off"]}, "headers": ["mpcg_scenario.h"]},
+    "mpcg_tracks.h": {"sources": {"mpcg_tracks.hip": ["-ffp-contract=off"]}, "headers": ["mpcg_tracks.h"]},
 }
 # csrc headers more than one layer includes: the entry points' checks and error text, the path evaluation,
 # the wave arg-min

@@ -12,7 +12,9 @@ per-step quantity device-resident.
 
 The scene data of the next step (ego state, obstacle predictions, guidance
 trajectories) comes from outside the planner (sensors, guidance_planner), so
-`set_scene_data` replaces it between steps.
+`set_scene_data` replaces it between steps.  With `set_tracks` the obstacle predictions
+come from a device-resident table of tracked objects instead (include/mpcg_tracks.h):
+every step() first fills obst / obst_meta from it.
 """
 from __future__ import annotations
 
@@ -64,6 +66,27 @@ class ControlLoop:
                                  f"{layout.n_lin} for {layout.max_obstacles} obstacles (tmpc_layout(add_halfspaces=2))")
             self._road = road.native()
             self.road_halfspaces = torch.zeros((self.S, layout.N, 2, 3), dtype=torch.float64, device=device)
+        # the table of tracked objects (set_tracks) or None: nothing is launched
+        self.tracks = None
+
+    def set_tracks(self, pose, twist, dims, shape, settings=None, propagate: bool = False):
+        """The tracked objects of every scene (include/mpcg_tracks.h): pose (S, A, 3), twist (S, A, 2), dims
+        (S, A, 2), shape (S, A) int32.  From now on every step() first fills obst / obst_meta from them
+        (mpcg_tracks_rows, mpcg_obstacle_select; `propagate`: the callback's second pass of
+        propagatePredictionUncertainty).  settings: tracks.TrackSettings (None: the defaults).  Device tensors
+        are taken as they are -- self.tracks holds them -- so the caller may update them in place between steps."""
+        from .tracks import TrackSettings
+
+        if self.lay.n_ell < 1:
+            raise ValueError("ControlLoop.set_tracks: the layout has no obstacle rows (n_ell 0)")
+        table = native.track_table_device(pose, twist, dims, shape, self.dev)
+        W, A = table["shape"].shape
+        if W != self.S:
+            raise ValueError(f"ControlLoop.set_tracks: {W} worlds for {self.S} scenes")
+        self._track_set = (TrackSettings() if settings is None else settings).native()
+        self._track_scratch = native.TrackObstacles(self.pr, self.S, A, self.dev)
+        self.track_propagate = bool(propagate)
+        self.tracks = table
 
     def set_road_path(self, dtable: dict, bounds: dict | None = None):
         """The path the road follows (native.path_table_device) and, for the bounds mode, the left and
@@ -99,6 +122,10 @@ class ControlLoop:
         a road)."""
         pr, S, G, N = self.pr, self.S, self.G, self.lay.N
         gl = self.guidance_layer
+        if self.tracks is not None:
+            native.tracks_obstacles_device(pr, self._track_set, self.tracks, self.dsc["state"], self.dsc["obst"],
+                                           self.dsc["obst_meta"], propagate=self.track_propagate,
+                                           scratch=self._track_scratch, stream=stream)
         if gl is not None:
             gl.update(self, stream=stream)
         if self.own_warm and self.last is not None:

@@ -1,6 +1,6 @@
 // mpcg_host.h — host-side plumbing shared by the entry points of the layers
 // (mpcg_fleet.hip, mpcg_path.hip, mpcg_guidance.hip, mpcg_active.hip, mpcg_road.hip, mpcg_decomp.hip,
-// mpcg_scenario.hip):
+// mpcg_scenario.hip, mpcg_tracks.hip):
 // the error text behind mpcg_last_error() and the argument checks more than one
 // entry point makes.  Host code only, internal; no kernel reads it.
 //

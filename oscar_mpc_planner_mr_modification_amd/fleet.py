@@ -254,6 +254,41 @@ class FleetLoop:
         self.reason = torch.zeros((S,), dtype=torch.int32, device=device)
         self.published = torch.zeros((S,), dtype=torch.uint8, device=device)
         self.array_obst = self.array_meta = self.array_id = None
+        # the table of the fleets' tracked objects (set_tracks) or None: nothing is launched
+        self.tracks = None
+
+    def set_tracks(self, pose, twist, dims, shape, settings=None):
+        """The fleets' non-communicating objects as tracked objects (include/mpcg_tracks.h), in place of
+        set_array_obstacles: pose (F, A, 3), twist (F, A, 2), dims (F, A, 2), shape (F, A) int32.  Every step
+        first runs mpcg_tracks_rows over the F worlds; its rows are what mpcg_fleet_obstacles then reads as
+        array_obst / array_meta, ids R + a.  Every slot must give exactly one row (UNSEEN, DISC, CYLINDER or a
+        square BOX; checked here on the host copy of shape and dims), so that row a is object a.  settings:
+        tracks.TrackSettings (None: the defaults with the fleet's probabilistic and risk).  Device tensors are
+        taken as they are -- self.tracks holds them -- so the caller may update them in place between steps
+        (a shape that changes must keep to the one-row shapes)."""
+        import torch
+
+        from . import native
+        from .tracks import TrackSettings, single_row_shapes
+
+        host = lambda a: a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)  # noqa: E731
+        if not single_row_shapes(host(shape), host(dims)):
+            raise ValueError("FleetLoop.set_tracks: every slot must give exactly one row (UNSEEN, DISC, CYLINDER or a "
+                             "square BOX)")
+        lp = self.loop
+        table = native.track_table_device(pose, twist, dims, shape, lp.dev)
+        W, A = table["shape"].shape
+        if W != self.F:
+            raise ValueError(f"FleetLoop.set_tracks: {W} worlds for {self.F} fleets")
+        if settings is None:
+            settings = TrackSettings(probabilistic=self.settings.probabilistic, risk=self.settings.risk)
+        self._track_set = settings.native()
+        self._track_rows = native.track_rows_buffers(self.F, A, lp.lay.N, lp.dev)
+        f64 = dict(dtype=torch.float64, device=lp.dev)
+        self.array_obst = torch.zeros((self.F, A, lp.lay.N, 5), **f64)
+        self.array_meta = torch.zeros((self.F, A, 2), **f64)
+        self.array_id = None
+        self.tracks = table
 
     def set_array_obstacles(self, array_obst, array_meta, array_id=None):
         """The fleets' non-communicating obstacles: array_obst (F, A, N, 5), array_meta (F, A, 2) rows as in
@@ -261,6 +296,7 @@ class FleetLoop:
         import torch
 
         dev = self.loop.dev
+        self.tracks = None
         self.array_obst = torch.as_tensor(array_obst, dtype=torch.float64, device=dev).contiguous()
         self.array_meta = torch.as_tensor(array_meta, dtype=torch.float64, device=dev).contiguous()
         self.array_id = None if array_id is None else torch.as_tensor(array_id, dtype=torch.int32,
@@ -271,9 +307,21 @@ class FleetLoop:
         topology id of every planner (None: the loop's guidance layer's class ids, or without a layer the
         planner index / 2 n_paths for the non-guided one).
         Returns ControlLoop.step's dict plus reason (S,) int32 and published (S,) uint8."""
+        import contextlib
+
+        import torch
+
         from . import native
 
         lp = self.loop
+        if self.tracks is not None:
+            # C = 2 A rows per world, of which the first A are written: the dense [F][A] rows
+            # mpcg_fleet_obstacles reads are their copy
+            A = self.array_obst.shape[1]
+            native.tracks_rows_device(lp.pr, self._track_set, self.tracks, out=self._track_rows, stream=stream)
+            with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+                self.array_obst.copy_(self._track_rows["rows"][:, :A])
+                self.array_meta.copy_(self._track_rows["rows_meta"][:, :A])
         native.fleet_obstacles_device(lp.pr, self.F, self.R, self._set, self.state, lp.dsc["state"], now,
                                       lp.dsc["obst"], lp.dsc["obst_meta"], self.array_obst, self.array_meta,
                                       self.array_id, stream=stream)

@@ -21,7 +21,8 @@ from .native_spec import (ABI_VERSION, ACTIVE_EXPORTS, DECOMP_EXPORTS, DEFAULT_O
                           UNICYCLE_UB, MpcgFleetSettings, MpcgFleetState, MpcgGuidanceOut, MpcgGuidanceSettings,
                           MpcgGuidanceState, MpcgIo, MpcgPathSettings, MpcgPathTable, MpcgProblem, MpcgRoadIo,
                           MpcgRoadSettings, MpcgSceneIo, MpcgStepIo, MpcgScenarioIo, ROAD_EXPORTS, problem_from_layout,
-                          OPEN_SIGNATURES, SCENARIO_EXPORTS, MpcgScenarioSampleIo, MpcgScenarioStepIo)
+                          OPEN_SIGNATURES, SCENARIO_EXPORTS, MpcgScenarioSampleIo, MpcgScenarioStepIo, TRACKS_EXPORTS,
+                          MpcgTrackSettings)
 
 PKG = os.path.dirname(os.path.abspath(__file__))
 # MPCG_LIB selects a diagnostic build (e.g. libmpcg_stamps.so); default the production library
@@ -653,6 +654,108 @@ def scenario_advance_device(pr: MpcgProblem, S: int, n_solvers: int, best, exit_
     rc = lib.mpcg_scenario_advance(C.byref(pr), S, n_solvers, C.byref(io), _ptr(main_warm), _ptr(lam_next),
                                    _stream(stream, xtraj.device))
     _check(rc, "mpcg_scenario_advance")
+
+
+def problem_with_rows(pr: MpcgProblem, n_ell: int) -> MpcgProblem:
+    """A copy of `pr` whose n_ell is `n_ell`: what mpcg_obstacle_select takes from a caller whose layout holds no
+    ellipsoid rows (SH-MPC: the number of predictions per scene).  The tracked-object layer reads N, dt, nx and
+    n_ell only."""
+    cp = MpcgProblem.from_buffer_copy(pr)
+    cp.n_ell = int(n_ell)
+    return cp
+
+
+def track_table_device(pose, twist, dims, shape, device) -> dict:
+    """The table of tracked objects (include/mpcg_tracks.h) as contiguous device tensors: pose (W, A, 3), twist
+    (W, A, 2), dims (W, A, 2) float64 and shape (W, A) int32.  Device tensors of the right type are taken as
+    they are, so the caller may update them in place between steps."""
+    f = lambda a: torch.as_tensor(a, dtype=F64, device=device).contiguous()  # noqa: E731
+    shape = torch.as_tensor(shape, dtype=I32, device=device).contiguous()
+    W, A = shape.shape
+    t = dict(pose=f(pose), twist=f(twist), dims=f(dims), shape=shape)
+    for k, n in (("pose", 3), ("twist", 2), ("dims", 2)):
+        _dev(k, t[k], F64, (W, A, n))
+    return t
+
+
+def track_rows_buffers(W: int, A: int, N: int, device) -> dict:
+    """The candidate rows of W worlds x A object slots, C = 2 A rows per world: what mpcg_tracks_rows writes and
+    mpcg_obstacle_select reads."""
+    C2 = 2 * A
+    return dict(rows=torch.zeros((W, C2, N, 5), dtype=F64, device=device),
+                rows_meta=torch.zeros((W, C2, 2), dtype=F64, device=device),
+                rows_type=torch.zeros((W, C2), dtype=I32, device=device),
+                n_rows=torch.zeros((W,), dtype=I32, device=device))
+
+
+def tracks_rows_device(pr: MpcgProblem, settings: MpcgTrackSettings, table: dict, out=None, stream=None) -> dict:
+    """mpcg_tracks_rows (include/mpcg_tracks.h): the constant-velocity predictions of every world's tracked objects
+    (`track_table_device`) as candidate rows.  Returns dict(rows (W, C, N, 5), rows_meta (W, C, 2), rows_type
+    (W, C) int32, n_rows (W,) int32), C = 2 A (`out` when given: nothing is allocated); rows past n_rows are not
+    written.  Asynchronous on `stream`."""
+    W, A = table["shape"].shape
+    _dev("shape", table["shape"], I32, (W, A))
+    for k, n in (("pose", 3), ("twist", 2), ("dims", 2)):
+        _dev(k, table[k], F64, (W, A, n))
+    dev = table["shape"].device
+    if out is None:
+        out = track_rows_buffers(W, A, pr.N, dev)
+    _dev("rows", out["rows"], F64, (W, 2 * A, pr.N, 5))
+    _dev("rows_meta", out["rows_meta"], F64, (W, 2 * A, 2))
+    _dev("rows_type", out["rows_type"], I32, (W, 2 * A))
+    _dev("n_rows", out["n_rows"], I32, W)
+    rc = lib.mpcg_tracks_rows(C.byref(pr), W, A, C.byref(settings), _ptr(table["pose"]), _ptr(table["twist"]),
+                              _ptr(table["dims"]), _ptr(table["shape"]), _ptr(out["rows"]), _ptr(out["rows_meta"]),
+                              _ptr(out["rows_type"]), _ptr(out["n_rows"]), _stream(stream, dev))
+    _check(rc, "mpcg_tracks_rows")
+    return out
+
+
+def obstacle_select_device(pr: MpcgProblem, settings: MpcgTrackSettings, cand: dict, state, obst, obst_meta,
+                           propagate: bool = False, kept=None, stream=None):
+    """mpcg_obstacle_select (include/mpcg_tracks.h): keep the n_ell closest of every scene's candidate rows
+    (`cand`: dict rows (S, max_rows, N, 5), rows_meta, rows_type, n_rows -- from tracks_rows_device or uploaded
+    finished) or pad with dummies, then with `propagate` one more pass of the uncertainty propagation, into obst
+    (S, n_ell, N, 5) / obst_meta (S, n_ell, 2); kept (S, n_ell) int32 or None: the candidate index of every
+    output row.  Asynchronous on `stream`; nothing is allocated."""
+    S, max_rows = cand["rows"].shape[0], cand["rows"].shape[1]
+    _dev("rows", cand["rows"], F64, (S, max_rows, pr.N, 5))
+    _dev("rows_meta", cand["rows_meta"], F64, (S, max_rows, 2))
+    _dev("rows_type", cand["rows_type"], I32, (S, max_rows))
+    _dev("n_rows", cand["n_rows"], I32, S)
+    _dev("state", state, F64, (S, pr.nx))
+    _dev("obst", obst, F64, (S, pr.n_ell, pr.N, 5))
+    _dev("obst_meta", obst_meta, F64, (S, pr.n_ell, 2))
+    if kept is not None:
+        _dev("kept", kept, I32, (S, pr.n_ell))
+    rc = lib.mpcg_obstacle_select(C.byref(pr), S, max_rows, C.byref(settings), _ptr(cand["rows"]),
+                                  _ptr(cand["rows_meta"]), _ptr(cand["rows_type"]), _ptr(cand["n_rows"]), _ptr(state),
+                                  int(bool(propagate)), _ptr(obst), _ptr(obst_meta), _ptr(kept),
+                                  _stream(stream, state.device))
+    _check(rc, "mpcg_obstacle_select")
+
+
+class TrackObstacles:
+    """tracks_obstacles_device's row scratch: the candidate rows of S scenes x A object slots, allocated once."""
+
+    def __init__(self, pr: MpcgProblem, S: int, A: int, device):
+        self.S, self.A = S, A
+        self.cand = track_rows_buffers(S, A, pr.N, device)
+
+
+def tracks_obstacles_device(pr: MpcgProblem, settings: MpcgTrackSettings, table: dict, state, obst, obst_meta,
+                            propagate: bool = False, scratch=None, kept=None, stream=None) -> TrackObstacles:
+    """mpcg_tracks_rows, then mpcg_obstacle_select: obst (S, n_ell, N, 5) / obst_meta (S, n_ell, 2) of every scene
+    from its tracked objects (scene s reads world s of `table`).  `scratch` (a TrackObstacles, returned) holds
+    the candidate rows between the two launches; with it nothing is allocated.  Asynchronous on `stream`."""
+    S, A = table["shape"].shape
+    if scratch is None:
+        scratch = TrackObstacles(pr, S, A, state.device)
+    assert (scratch.S, scratch.A) == (S, A), ((scratch.S, scratch.A), (S, A))
+    tracks_rows_device(pr, settings, table, out=scratch.cand, stream=stream)
+    obstacle_select_device(pr, settings, scratch.cand, state, obst, obst_meta, propagate=propagate, kept=kept,
+                           stream=stream)
+    return scratch
 
 
 def _guidance_state(gstate: dict, S: int, G: int, N: int) -> MpcgGuidanceState:

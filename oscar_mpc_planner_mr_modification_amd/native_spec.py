@@ -371,14 +371,29 @@ SCENARIO_MIX_C1, SCENARIO_MIX_C2 = 0x9E3779B97F4A7C15, 0xD1B54A32D192ED03
 SCENARIO_MIX_M1, SCENARIO_MIX_M2 = 0xBF58476D1CE4E5B9, 0x94D049BB133111EB
 
 
+class MpcgTrackSettings(C.Structure):
+    """Mirror of `mpcg_track_settings` (include/mpcg_tracks.h)."""
+    _fields_ = [("obstacle_radius", C.c_double), ("probabilistic", C.c_int), ("chi_gaussian", C.c_double)]
+
+
+# the tracked-object layer (include/mpcg_tracks.h)
+TRACK_NONE, TRACK_UNSEEN, TRACK_DISC, TRACK_CYLINDER, TRACK_BOX = -1, 0, 1, 2, 3
+TRACKS_MAX_N, TRACKS_MAX_OBJECTS, TRACKS_MAX_ROWS, TRACKS_MAX_ELL = 32, 32, 64, 32
+
+
 def _open_signatures() -> dict:
     i, vp, ptr = C.c_int, C.c_void_p, C.POINTER
     P, SIO = ptr(MpcgProblem), ptr(MpcgScenarioSampleIo)
+    TS = ptr(MpcgTrackSettings)
     return {
         "mpcg_scenario.h": {
             "mpcg_scenario_sample_prepare": (i, [P, i, i, SIO, vp, vp, vp, vp]),
             "mpcg_scenario_samples": (i, [P, i, i, SIO, vp, vp]),
             "mpcg_scenario_advance": (i, [P, i, i, ptr(MpcgScenarioStepIo), vp, vp, vp]),
+        },
+        "mpcg_tracks.h": {
+            "mpcg_tracks_rows": (i, [P, i, i, TS] + [vp] * 9),
+            "mpcg_obstacle_select": (i, [P, i, i, TS, vp, vp, vp, vp, vp, i, vp, vp, vp, vp]),
         },
     }
 
@@ -387,3 +402,4 @@ def _open_signatures() -> dict:
 # (tests/test_layer_abi_open.py pins no key set); native._load() applies all three tables in one loop.
 OPEN_SIGNATURES = _open_signatures()
 SCENARIO_EXPORTS = tuple(OPEN_SIGNATURES["mpcg_scenario.h"])
+TRACKS_EXPORTS = tuple(OPEN_SIGNATURES["mpcg_tracks.h"])

@@ -307,6 +307,10 @@ class PathLoop:
             self.loop.set_road_path(self.table, self._native.road_bounds_device(left_coef, right_coef, self.loop.dev)
                                     if both else None)
 
+    def set_tracks(self, pose, twist, dims, shape, **options):
+        """ControlLoop.set_tracks of the inner loop: the obstacle predictions from tracked objects."""
+        self.loop.set_tracks(pose, twist, dims, shape, **options)
+
     def step(self, stream=None):
         """One control step of every scene.  Returns ControlLoop.step's dict plus closest_segment,
         closest_s, reached, cmd (S, 2) and, with the plant, state_next (S, nx)."""

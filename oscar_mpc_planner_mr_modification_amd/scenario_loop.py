@@ -8,7 +8,8 @@ device-resident and the obstacle samples drawn on the device (include/mpcg_scena
     advance():  mpcg_scenario_advance (warm start and multipliers of the next step)
 
 The scene data of the next step (ego state, obstacle predictions) comes from outside the planner, so
-`set_scene_data` replaces it between steps.  Every buffer is allocated in the constructor; step() and
+`set_scene_data` replaces it between steps; with `set_tracks` the predictions come from a device-resident table
+of tracked objects instead (include/mpcg_tracks.h), filled in first by every step().  Every buffer is allocated in the constructor; step() and
 advance() allocate nothing and synchronise nothing when they are given device tensors.  `draw`, the
 step counter of the derived batch index, advances by one per step().
 """
@@ -56,6 +57,28 @@ class ScenarioLoop:
         self.best = torch.empty((S,), dtype=torch.int32, device=device)
         self.records = torch.empty((S, (N + 1) * nx + N * nu + 2), **f64)
         self.last = None
+        # the table of tracked objects (set_tracks) or None: nothing is launched
+        self.tracks = None
+
+    def set_tracks(self, pose, twist, dims, shape, settings=None, propagate: bool = False):
+        """The tracked objects of every scene (include/mpcg_tracks.h): pose (S, A, 3), twist (S, A, 2), dims
+        (S, A, 2), shape (S, A) int32.  From now on every step() first fills the predictions obst / obst_meta --
+        what mpcg_scenario_sample_prepare reads -- from them (mpcg_tracks_rows, mpcg_obstacle_select; `propagate`:
+        the callback's second pass of propagatePredictionUncertainty).  settings: tracks.TrackSettings (None: the
+        defaults with probabilistic on, SH-MPC's GAUSSIAN predictions).  Device tensors are taken as they are --
+        self.tracks holds them -- so the caller may update them in place between steps."""
+        from .tracks import TrackSettings
+
+        # the SH-MPC layout has no ellipsoid rows: the selection's n_ell is the loop's predictions per scene
+        self._track_pr = native.problem_with_rows(self.pr, self.obst.shape[1])
+        table = native.track_table_device(pose, twist, dims, shape, self.dev)
+        W, A = table["shape"].shape
+        if W != self.S:
+            raise ValueError(f"ScenarioLoop.set_tracks: {W} worlds for {self.S} scenes")
+        self._track_set = (TrackSettings(probabilistic=True) if settings is None else settings).native()
+        self._track_scratch = native.TrackObstacles(self._track_pr, self.S, A, self.dev)
+        self.track_propagate = bool(propagate)
+        self.tracks = table
 
     def set_scene_data(self, state, obst, obst_meta=None):
         """Replace the externally provided scene data: state (S, nx), obst (S, n_obs, N, 5) and optionally
@@ -71,6 +94,9 @@ class ScenarioLoop:
         draw): the loop's own buffers, overwritten by the next step."""
         pr, S, P = self.pr, self.S, self.P
         draw = self.draw
+        if self.tracks is not None:
+            native.tracks_obstacles_device(self._track_pr, self._track_set, self.tracks, self.state, self.obst, self.obst_meta,
+                                           propagate=self.track_propagate, scratch=self._track_scratch, stream=stream)
         native.scenario_sample_prepare_device(pr, P, self.stage_params, self.state, self.obst, self.obst_meta,
                                               self.bank, self.rr, self.dec,
                                               main_warm=self.main_warm if self.has_warm else None, seed=self.seed,
